@@ -25,6 +25,12 @@ Besides the contract fields the line carries
                 un-instrumented), algorithmic FLOPs/bytes per SURVEY.md §8(d);
   cpu_baseline  the CPU oracle (numpy per-offset gather-GEMM-scatter restatement of spconv's CPU algorithm, all
                 host cores, + torch-CPU dense tail) timed on a bounded sample: one frame of the same workload.
+
+`--dump-outputs DIR` (rank 0) writes what the LAST timed step computed, one DIR/<name>.npy per array (float32, or float64
+for float64 and integer data): in training `loss`, `tb.<key>` (the loss terms), `grad.<parameter>` (after clipping) and
+`param.<parameter>` (after the optimizer step); in the forward modes the detector's outputs.  Inputs and initial weights
+are seeded, so two builds run with the same arguments can be compared array by array.  At most 64 MB in all: above that,
+every array larger than 4096 elements is replaced by a fixed, seeded sample of its flattened elements (sorted indices).
 """
 import argparse
 import json
@@ -77,7 +83,12 @@ def parse():
                     help="training with exact-size sparse tensors (one host read per strided rule table) instead of the "
                          "host-sync-free static-capacity path")
     ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 DENSE_LAYOUT = "nhwc"
@@ -138,24 +149,29 @@ class Step(object):
                 from pcdet_amd.models.inference import GraphedDetector
                 core = self.model.module if hasattr(self.model, "module") else self.model
                 self.runner = GraphedDetector(core, batch["batch_size"], int(batch["points"].shape[0] * 1.05) + 64)
-            return self.runner(batch["points"])["batch_box_preds"]
+            self.last = self.runner(batch["points"])           # static buffers: read before the next replay
+            return self.last["batch_box_preds"]
         if self.mode == "fwd":
             with torch.no_grad():
                 for m in (self.model.module if hasattr(self.model, "module") else self.model).module_list:
                     bd = m(bd)
+            self.last = {k: bd[k] for k in ("batch_cls_preds", "batch_box_preds") if k in bd}
             return bd["batch_box_preds"]
         self.sched.step(self.it)
         if getattr(self, "graphed", None) is not None:
             # forward + backward = one hipGraph replay (pcdet_amd/models/inference.py:GraphedTrainStep); gradients are
             # rewritten in place by the replay, so no zero_grad
-            loss = self.graphed(batch["points"], batch["gt_boxes"])["loss"]
+            out = self.graphed(batch["points"], batch["gt_boxes"])
+            loss = out["loss"]
+            self.last = {"loss": loss, "tb": out.get("tb_dict") or {}}
         else:
             self.opt.zero_grad(set_to_none=True)
             if self.static_caps is not None:
                 bd["static_caps"] = self.static_caps
-            ret, _tb, _ = self.model(bd)
+            ret, tb, _ = self.model(bd)
             loss = ret["loss"].mean()
             loss.backward()
+            self.last = {"loss": loss, "tb": tb}
         torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip, foreach=True)
         self.opt.step()
         self.it += 1
@@ -690,6 +706,58 @@ def extras(core, batches, batch, device, args):
     return out
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_BUDGET = 64_000_000       # bytes over all files written by --dump-outputs
+DUMP_SMALL = 4096              # arrays up to this many elements are always written whole
+
+
+def _host(t):
+    """float64 and integer / bool data -> float64 (exact), every other float -> float32; on the host."""
+    t = t.detach()
+    if t.dtype == torch.float64 or not t.is_floating_point():
+        return t.to("cpu", torch.float64).numpy()
+    return t.to("cpu", torch.float32).numpy()
+
+
+def step_outputs(step, model):
+    """name -> host array of what the last call of `step` computed: its outputs (nested dicts flattened to dotted names)
+    and, in training, every parameter's gradient and new value."""
+    out = {}
+
+    def walk(prefix, obj):
+        if isinstance(obj, dict):
+            for k, v in obj.items():
+                walk(prefix + str(k) + ".", v)
+        elif torch.is_tensor(obj):
+            out[prefix[:-1]] = _host(obj)
+    walk("", step.last)
+    if step.mode == "train":
+        core = model.module if hasattr(model, "module") else model
+        for name, p in core.named_parameters():
+            if p.grad is not None:
+                out["grad." + name] = _host(p.grad)
+            out["param." + name] = _host(p)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` as out_dir/<name>.npy within DUMP_BUDGET bytes: if they do not fit, every array above DUMP_SMALL
+    elements is cut to the same fraction of its elements, chosen by a generator seeded from its name (same sample in
+    every run)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BUDGET - 256 * len(arrays)                    # .npy headers
+    small = sum(a.nbytes for a in arrays.values() if a.size <= DUMP_SMALL)
+    big = sum(a.nbytes for a in arrays.values() if a.size > DUMP_SMALL)
+    keep = 1.0 if small + big <= budget else max(budget - small, 0) / big
+    for name, a in arrays.items():
+        if keep < 1.0 and a.size > DUMP_SMALL:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` outside torchrun: start the N ranks as children (one process per GPU, RCCL rendezvous on
     127.0.0.1) from a parent that never initialises the GPU — torch.cuda.device_count() does not — and hand their exit
@@ -812,6 +880,8 @@ def main():
         dt = float(t.item())
     from spx import ops as _ops
     _ops.check_status(device)      # a static capacity that overflowed (rows dropped) would invalidate the number: raises
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(step, model))     # before the instrumented steps overwrite them
 
     line = None
     if rank == 0:

@@ -135,6 +135,58 @@ def test_bench_launcher_refuses_what_it_cannot_run():
     assert r.returncode == 2 and "WORLD_SIZE=4" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float32 / float64 files only, whole when they fit, otherwise a seeded sample of the large
+    arrays that keeps the total within the budget and is the same from run to run.  Host-only: no GPU touched."""
+    import bench
+    arrays = {"loss": bench._host(torch.tensor(1.5)), "count": bench._host(torch.tensor([3, 4], dtype=torch.int32)),
+              "grad.w": bench._host(torch.arange(100_000, dtype=torch.float32)),
+              "preds": bench._host(torch.arange(50_000, dtype=torch.float64)),
+              "half": bench._host(torch.full((7,), 0.5, dtype=torch.float16))}
+    assert arrays["count"].dtype == np.float64 and arrays["preds"].dtype == np.float64 and arrays["half"].dtype == np.float32
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "whole" / (k + ".npy")), a)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 200_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 200_000
+    for k, a in arrays.items():
+        x, y = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert np.array_equal(x, y) and x.dtype in (np.float32, np.float64)
+        if a.size <= bench.DUMP_SMALL:
+            assert np.array_equal(x, a)
+        else:
+            assert 0 < x.size < a.size and np.all(np.diff(x) > 0) and np.isin(x, a).all()    # sorted sample of the array
+
+
+@pytest.mark.parametrize("transposed,k,s,p", [(False, 3, 2, 1), (False, 3, 1, 1), (True, 2, 2, 0), (True, 1, 1, 0)])
+def test_fixed_order_conv_weight_gradient(transposed, k, s, p, monkeypatch):
+    """model_utils/det_wgrad: the fixed-order weight gradient of the BEV tail's stock convolutions (and its data gradient)
+    equals autograd's for conv2d / conv_transpose2d.  CHUNK = 16 puts every case on the chunked branch with a remainder
+    (the stride-2 conv: 7 x 6 = 42 output pixels per sample = 2 chunks + 10)."""
+    import torch.nn.functional as F
+    from pcdet_amd.models.model_utils import det_wgrad
+    monkeypatch.setattr(det_wgrad, "CHUNK", 16)
+    calls = []
+    bmm = torch.bmm
+    monkeypatch.setattr(torch, "bmm", lambda *a: calls.append(a[0].shape) or bmm(*a))
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(2, 8, 13, 11, dtype=torch.float64, generator=g, requires_grad=True)
+    w = torch.randn(*((8, 6, k, k) if transposed else (6, 8, k, k)), dtype=torch.float64, generator=g, requires_grad=True)
+    y = det_wgrad._ConvFn.apply(x, w, s, p, transposed)
+    ref = F.conv_transpose2d(x, w, None, s) if transposed else F.conv2d(x, w, None, s, p)
+    assert torch.equal(y, ref)
+    dy = torch.randn(ref.shape, dtype=torch.float64, generator=g)
+    for a, b in zip(torch.autograd.grad(y, (x, w), dy), torch.autograd.grad(ref, (x, w), dy)):
+        assert torch.allclose(a, b, rtol=1e-12, atol=1e-12)
+    assert calls and all(c[0] >= 2 for c in calls)                    # the chunked reduction ran
+    a, b = torch.randn(1000, 5, dtype=torch.float64, generator=g), torch.randn(1000, 7, dtype=torch.float64, generator=g)
+    assert torch.allclose(det_wgrad.rows_tn(a, b), a.t() @ b, rtol=1e-12, atol=1e-12)
+    dw, db = det_wgrad.pointwise_wgrad(b, a)
+    assert torch.allclose(dw, b.t() @ a, rtol=1e-12, atol=1e-12) and torch.allclose(db, b.sum(0))
+
+
 def test_bn_momentum_none_is_not_fused():
     """nn.BatchNorm with momentum=None keeps a cumulative average; the fused kernels take a fixed factor, so such a module
     must stay on the torch path."""

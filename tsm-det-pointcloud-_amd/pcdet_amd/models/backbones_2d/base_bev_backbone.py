@@ -11,6 +11,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from spx import ops
+
+from ..model_utils import det_wgrad
 from spx.functional import (bn_relu_cat_train, bn_relu_train, dense as densify_rows, folded_bn, sparse_conv, wino_conv2d,
                             wino_conv2d_ok, wino_conv_bn_relu_train)
 
@@ -37,7 +39,10 @@ def _run_block(seq, x, start=0):
         if (isinstance(m, nn.ZeroPad2d) and isinstance(nxt, nn.Conv2d) and tuple(nxt.padding) == (0, 0)
                 and nxt.padding_mode == 'zeros' and len(set(m.padding)) == 1 and isinstance(nxt.padding, tuple)):
             p = int(m.padding[0])
-            x = F.conv2d(x, nxt.weight, nxt.bias, nxt.stride, (p, p), nxt.dilation, nxt.groups)
+            if det_wgrad.usable(x, nxt):
+                x = det_wgrad.conv2d(x, nxt, p)               # weight gradient in a fixed summation order
+            else:
+                x = F.conv2d(x, nxt.weight, nxt.bias, nxt.stride, (p, p), nxt.dilation, nxt.groups)
             i += 2
             continue
         if _WINO and isinstance(m, nn.Conv2d) and wino_conv2d_ok(x, m):
@@ -72,9 +77,14 @@ def _run_block(seq, x, start=0):
             x = y.view(b, h, w, c).permute(0, 3, 1, 2)
             i += 2
             continue
-        x = m(x)
+        x = _up(m, x) if isinstance(m, nn.ConvTranspose2d) else m(x)
         i += 1
     return x
+
+
+def _up(m, x):
+    """m(x) for an up-sampling ConvTranspose2d; in training its weight gradient in a fixed summation order."""
+    return det_wgrad.conv_transpose2d(x, m) if det_wgrad.usable(x, m) else m(x)
 
 
 _FUSED_EVAL_BN = os.environ.get("SPX_BEV_FUSED_EVAL_BN", "1") != "0"       # dev knob
@@ -237,7 +247,7 @@ class BaseBEVBackbone(nn.Module):
             stride = int(spatial_features.shape[2] / x.shape[2])
             data_dict['spatial_features_%dx' % stride] = x
             if fuse_cat or fuse_cat_eval:
-                pre.append(self.deblocks[i][0](x))                      # the up-sampling conv; BN + ReLU follow below
+                pre.append(_up(self.deblocks[i][0], x))                      # the up-sampling conv; BN + ReLU follow below
             else:
                 ups.append(_run_block(self.deblocks[i], x) if len(self.deblocks) > 0 else x)
         if fuse_cat or fuse_cat_eval:

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..model_utils import det_wgrad
 from .anchor_head_template import AnchorHeadTemplate
 
 
@@ -16,9 +17,9 @@ _HYBRID = os.environ.get("SPX_HEAD_HYBRID", "1") != "0"      # dev knob
 class _PointwiseHeadsFn(torch.autograd.Function):
     """1x1 convolution of a channels_last map as the three GEMM-shaped pieces that are fastest on MI355X for a 512 -> 72
     head (tools/dense_tail_probe.py, 4 x 200 x 176 pixels): forward = one GEMM over pixels (155 us; MIOpen's conv 267),
-    input gradient = one GEMM (dy @ W), weight / bias gradient = MIOpen's conv backward-weights (which reduces over the
-    141 k pixels better than a GEMM with that K).  fwd+bwd 489 us against 666 for conv2d's own backward.  Same dot
-    products as the three 1x1 convs of reference anchor_head_single.py:54-68."""
+    input gradient = one GEMM (dy @ W), weight / bias gradient on the GPU = GEMMs over fixed chunks of the 141 k pixels
+    summed in a fixed order (model_utils/det_wgrad.py: MIOpen's backward-weights reduces in a run-dependent order).  Same dot products
+    as the three 1x1 convs of reference anchor_head_single.py:54-68."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -31,9 +32,12 @@ class _PointwiseHeadsFn(torch.autograd.Function):
         dy = dy.contiguous()
         n, h, wd, co = dy.shape
         dx = (dy.view(-1, co) @ w.flatten(1)).view(n, h, wd, x.shape[1]).permute(0, 3, 1, 2)
-        _, dw, db = torch.ops.aten.convolution_backward(dy.permute(0, 3, 1, 2), x, w, [co], [1, 1], [0, 0], [1, 1], False,
-                                                        [0, 0], 1, [False, True, True])
-        return dx, dw, db
+        if not dy.is_cuda:
+            _, dw, db = torch.ops.aten.convolution_backward(dy.permute(0, 3, 1, 2), x, w, [co], [1, 1], [0, 0], [1, 1],
+                                                            False, [0, 0], 1, [False, True, True])
+            return dx, dw, db
+        dw, db = det_wgrad.pointwise_wgrad(dy.view(-1, co), x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]))
+        return dx, dw.view_as(w), db
 
 
 class AnchorHeadSingle(AnchorHeadTemplate):
