@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SPX_ABI_VERSION 2
+#define SPX_ABI_VERSION 3
 
 #define SPX_OK 0
 #define SPX_ERR_INVALID_ARG (-1)  /* null pointer, non-positive extent, kernel volume > SPX_MAX_KVOL ... */
@@ -461,6 +461,69 @@ int spx_voxel_query_dilated(const float *new_xyz, const float *xyz, const int32_
                             const int32_t *point_indices, int64_t m, int batch, const int32_t *shape3, int nsample,
                             float former_radius, float radius, const int32_t *range3, const int32_t *stride3,
                             int32_t *idx, int32_t *cnt_unique, int32_t *idx_cnt, spx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 11. Point sampling and grouping (the fork's 3DSSD-style SA layers; csrc/pointnet2.hip)
+ *    replaces: the pointnet2_batch extension, reference pcdet/ops/pointnet2/pointnet2_batch/src/ (sampling, ball_query,
+ *      group_points, interpolate _gpu.cu), reached from
+ *      pointnet2_utils.py and _VoxelPointnetSAModuleFSDistillationBase (pointnet2_modules.py:1140-1230, 1514-1540).
+ *    All tensors fp32 / int32, contiguous, batch-major; b frames.  Distances are ((dx*dx)+(dy*dy))+(dz*dz) rounded after
+ *    every operation (no FMA contraction).  Indices outside [0, N) are a caller error; the kernels skip them (forward:
+ *    read as 0, backward: dropped) and never access memory out of bounds.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* replaces: furthest_point_sampling_wrapper / farthest_point_sampling_wrapper (sampling_gpu.cu, python side
+ *   pointnet2_utils.py:21-38, 85-111) and, with weights, furthest_point_sampling_weights_wrapper (:62-81).
+ *   xyz [b, n, 3]; weights [b, n] or NULL; idx [b, npoint] out.  Unweighted: idx[0] = 0; weighted: round 0 picks the
+ *   arg-max of the weights.  Later rounds: temp[k] = min(temp[k], |p_k - p_old|^2) (temp starts at 1e10), next pick =
+ *   arg-max of temp[k] (weighted: of (float)((double)temp[k] * max((double)w_k, 1e-12))).  Ties resolve exactly as the
+ *   reference's thread layout does (csrc/pointnet2.hip).  npoint > n is legal.  n <= 16384 runs with points and temp in
+ *   registers (ws unused, ws_bytes() = 0); larger n keeps temp in ws. */
+size_t spx_furthest_point_sample_ws_bytes(int32_t b, int64_t n);
+int spx_furthest_point_sample(const float *xyz, const float *weights, int32_t b, int64_t n, int32_t npoint, int32_t *idx,
+                              void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* replaces: furthest_point_sampling_matrix_wrapper, furthest_point_sampling_with_dist_wrapper and (weights non-NULL)
+ *   furthest_point_sampling_with_weighted_dist_wrapper (pointnet2_utils.py:42-58, 114-169).  matrix [b, n, n]: the
+ *   distance of round r is matrix[old][k]; otherwise as spx_furthest_point_sample.  ws: temp, b*n floats. */
+size_t spx_furthest_point_sample_matrix_ws_bytes(int32_t b, int64_t n);
+int spx_furthest_point_sample_matrix(const float *matrix, const float *weights, int32_t b, int64_t n, int32_t npoint,
+                                     int32_t *idx, void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* replaces: ball_query_wrapper (r_in = 0) and ball_query_dilated_wrapper (ball_query_gpu.cu:75-198, python side
+ *   pointnet2_utils.py:414-457).  xyz [b, n, 3]; new_xyz [b, m, 3] centres; hits are the k (ascending) with
+ *   r_in^2 <= d2 < r_out^2, the first nsample kept; idx_cnt [b, m] = hits kept; idx [b, m, nsample]: the hits, then the
+ *   hits repeated cyclically; an empty ball is all 0.  Every slot is written (no pre-zeroing needed). */
+int spx_ball_query(const float *xyz, const float *new_xyz, int32_t b, int64_t n, int64_t m, float r_in, float r_out,
+                   int32_t nsample, int32_t *idx_cnt, int32_t *idx, spx_stream_t stream);
+
+/* replaces: group_points_wrapper (group_points_gpu.cu, pointnet2_utils.py:340-361) and, with nsample = 1,
+ *   gather_points_wrapper (sampling_gpu.cu:15-50, pointnet2_utils.py:223-244).  features [b, c, n]; idx [b, m, nsample];
+ *   out [b, c, m, nsample] = features[.., idx]. */
+int spx_group_points(const float *features, const int32_t *idx, int32_t b, int32_t c, int64_t n, int64_t m,
+                     int32_t nsample, float *out, spx_stream_t stream);
+
+/* replaces: group_points_grad_wrapper / gather_points_grad_wrapper (atomicAdd there).  grad_features [b, c, n] (fully
+ *   written) = sum of grad_out over the entries that point at each feature, DETERMINISTIC: the entries are sorted by
+ *   target (stable radix sort in ws) and each target's contributions are added in ascending entry order. */
+size_t spx_group_points_bwd_ws_bytes(int32_t b, int64_t n, int64_t m, int32_t nsample);
+int spx_group_points_bwd(const float *grad_out, const int32_t *idx, int32_t b, int32_t c, int64_t n, int64_t m,
+                         int32_t nsample, float *grad_features, void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* replaces: three_nn_wrapper (interpolate_gpu.cu:16-75, pointnet2_utils.py:260-289).  unknown [b, n, 3], known [b, m, 3];
+ *   dist2 [b, n, 3] squared distances and idx [b, n, 3] of the three nearest known points (strict-< insertion in
+ *   ascending k: the first index wins ties; m < 3 leaves inf and index 0 in the unfilled slots). */
+int spx_three_nn(const float *unknown, const float *known, int32_t b, int64_t n, int64_t m, float *dist2, int32_t *idx,
+                 spx_stream_t stream);
+
+/* replaces: three_interpolate_wrapper / three_interpolate_grad_wrapper (interpolate_gpu.cu, pointnet2_utils.py:292-334).
+ *   features [b, c, m]; idx, weight [b, n, 3]; out [b, c, n] = ((w0*f0) + (w1*f1)) + (w2*f2).  The backward writes all
+ *   of grad_features [b, c, m], deterministically as spx_group_points_bwd does. */
+int spx_three_interpolate(const float *features, const int32_t *idx, const float *weight, int32_t b, int32_t c, int64_t m,
+                          int64_t n, float *out, spx_stream_t stream);
+size_t spx_three_interpolate_bwd_ws_bytes(int32_t b, int64_t m, int64_t n);
+int spx_three_interpolate_bwd(const float *grad_out, const int32_t *idx, const float *weight, int32_t b, int32_t c,
+                              int64_t m, int64_t n, float *grad_features, void *ws, size_t ws_bytes, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede CDLL — see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPX_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libspx.so")   # SPX_LIB_PATH: dev override (A/B of two builds)
 
-SPX_ABI_VERSION = 2
+SPX_ABI_VERSION = 3
 SPX_MAX_KVOL = 32
 
 _vp = ctypes.c_void_p
@@ -94,6 +94,20 @@ SIGNATURES = {
                                _vp]),
     "spx_assign_targets": (_int, [_vp, _int, _i64, _int, _vp, _int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                   _vp]),
+    "spx_furthest_point_sample_ws_bytes": (_sz, [ctypes.c_int32, _i64]),
+    "spx_furthest_point_sample": (_int, [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _vp, _sz, _vp]),
+    "spx_furthest_point_sample_matrix_ws_bytes": (_sz, [ctypes.c_int32, _i64]),
+    "spx_furthest_point_sample_matrix": (_int, [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _vp, _sz, _vp]),
+    "spx_ball_query": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_int32, _vp,
+                              _vp, _vp]),
+    "spx_group_points": (_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp]),
+    "spx_group_points_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, _i64, ctypes.c_int32]),
+    "spx_group_points_bwd": (_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp, _sz,
+                                    _vp]),
+    "spx_three_nn": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp, _vp]),
+    "spx_three_interpolate": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, _vp, _vp]),
+    "spx_three_interpolate_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, _i64]),
+    "spx_three_interpolate_bwd": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -918,3 +918,124 @@ def voxel_query_dilated(new_xyz, xyz, new_coords, point_indices, nsample, former
                                       i3(strides), _ptr(idx), _ptr(cnt), _ptr(filled), _stream(xyz)),
           "spx_voxel_query_dilated")
     return idx, cnt, filled
+
+
+# ------------------------------------------------------------------------------------------- point sampling (§11)
+
+def _f32(t):
+    return t.detach().contiguous().float()
+
+
+def _i32(t):
+    return t.detach().contiguous().int()
+
+
+def furthest_point_sample(xyz, npoint, weights=None):
+    """spx_furthest_point_sample: xyz (B, N, 3), weights (B, N) or None -> idx (B, npoint) int32."""
+    _need_gpu(xyz, weights)
+    lib = _lib.load()
+    xyz = _f32(xyz)
+    weights = None if weights is None else _f32(weights)
+    b, n, _ = xyz.shape
+    idx = torch.empty((b, int(npoint)), dtype=torch.int32, device=xyz.device)
+    wsb = lib.spx_furthest_point_sample_ws_bytes(b, n)
+    ws = workspace(xyz.device, wsb) if wsb else None
+    check(lib.spx_furthest_point_sample(_ptr(xyz), _ptr(weights), b, n, int(npoint), _ptr(idx), _ptr(ws), wsb,
+                                        _stream(xyz)), "spx_furthest_point_sample")
+    return idx
+
+
+def furthest_point_sample_matrix(matrix, npoint, weights=None):
+    """spx_furthest_point_sample_matrix: matrix (B, N, N) pairwise distances, weights (B, N) or None -> idx (B, npoint)."""
+    _need_gpu(matrix, weights)
+    lib = _lib.load()
+    matrix = _f32(matrix)
+    weights = None if weights is None else _f32(weights)
+    b, n, _ = matrix.shape
+    idx = torch.empty((b, int(npoint)), dtype=torch.int32, device=matrix.device)
+    wsb = lib.spx_furthest_point_sample_matrix_ws_bytes(b, n)
+    ws = workspace(matrix.device, wsb)
+    check(lib.spx_furthest_point_sample_matrix(_ptr(matrix), _ptr(weights), b, n, int(npoint), _ptr(idx), _ptr(ws), wsb,
+                                               _stream(matrix)), "spx_furthest_point_sample_matrix")
+    return idx
+
+
+def ball_query(xyz, new_xyz, nsample, r_out, r_in=0.0):
+    """spx_ball_query: -> idx_cnt (B, M), idx (B, M, nsample) int32 (hits r_in^2 <= d2 < r_out^2, padded cyclically)."""
+    _need_gpu(xyz, new_xyz)
+    lib = _lib.load()
+    xyz, new_xyz = _f32(xyz), _f32(new_xyz)
+    b, n, _ = xyz.shape
+    m = new_xyz.shape[1]
+    idx_cnt = torch.empty((b, m), dtype=torch.int32, device=xyz.device)
+    idx = torch.empty((b, m, int(nsample)), dtype=torch.int32, device=xyz.device)
+    check(lib.spx_ball_query(_ptr(xyz), _ptr(new_xyz), b, n, m, float(r_in), float(r_out), int(nsample), _ptr(idx_cnt),
+                             _ptr(idx), _stream(xyz)), "spx_ball_query")
+    return idx_cnt, idx
+
+
+def group_points(features, idx):
+    """spx_group_points: features (B, C, N), idx (B, M, S) -> (B, C, M, S); idx (B, M) -> (B, C, M) (gather)."""
+    _need_gpu(features, idx)
+    lib = _lib.load()
+    features, idx = _f32(features), _i32(idx)
+    b, c, n = features.shape
+    m, s = idx.shape[1], (idx.shape[2] if idx.dim() == 3 else 1)
+    out = torch.empty((b, c) + tuple(idx.shape[1:]), dtype=torch.float32, device=features.device)
+    check(lib.spx_group_points(_ptr(features), _ptr(idx), b, c, n, m, s, _ptr(out), _stream(features)), "spx_group_points")
+    return out
+
+
+def group_points_bwd(grad_out, idx, n):
+    """spx_group_points_bwd: grad_out (B, C, M[, S]) -> grad_features (B, C, n), summed in a fixed order."""
+    _need_gpu(grad_out, idx)
+    lib = _lib.load()
+    grad_out, idx = _f32(grad_out), _i32(idx)
+    b, c = grad_out.shape[:2]
+    m, s = idx.shape[1], (idx.shape[2] if idx.dim() == 3 else 1)
+    grad = torch.empty((b, c, int(n)), dtype=torch.float32, device=grad_out.device)
+    wsb = lib.spx_group_points_bwd_ws_bytes(b, n, m, s)
+    ws = workspace(grad_out.device, wsb)
+    check(lib.spx_group_points_bwd(_ptr(grad_out), _ptr(idx), b, c, int(n), m, s, _ptr(grad), _ptr(ws), wsb,
+                                   _stream(grad_out)), "spx_group_points_bwd")
+    return grad
+
+
+def three_nn(unknown, known):
+    """spx_three_nn: unknown (B, n, 3), known (B, m, 3) -> dist2 (B, n, 3) squared, idx (B, n, 3) int32."""
+    _need_gpu(unknown, known)
+    lib = _lib.load()
+    unknown, known = _f32(unknown), _f32(known)
+    b, n, _ = unknown.shape
+    m = known.shape[1]
+    dist2 = torch.empty((b, n, 3), dtype=torch.float32, device=unknown.device)
+    idx = torch.empty((b, n, 3), dtype=torch.int32, device=unknown.device)
+    check(lib.spx_three_nn(_ptr(unknown), _ptr(known), b, n, m, _ptr(dist2), _ptr(idx), _stream(unknown)), "spx_three_nn")
+    return dist2, idx
+
+
+def three_interpolate(features, idx, weight):
+    """spx_three_interpolate: features (B, C, m), idx / weight (B, n, 3) -> (B, C, n)."""
+    _need_gpu(features, idx, weight)
+    lib = _lib.load()
+    features, idx, weight = _f32(features), _i32(idx), _f32(weight)
+    b, c, m = features.shape
+    n = idx.shape[1]
+    out = torch.empty((b, c, n), dtype=torch.float32, device=features.device)
+    check(lib.spx_three_interpolate(_ptr(features), _ptr(idx), _ptr(weight), b, c, m, n, _ptr(out), _stream(features)),
+          "spx_three_interpolate")
+    return out
+
+
+def three_interpolate_bwd(grad_out, idx, weight, m):
+    """spx_three_interpolate_bwd: grad_out (B, C, n) -> grad_features (B, C, m), summed in a fixed order."""
+    _need_gpu(grad_out, idx, weight)
+    lib = _lib.load()
+    grad_out, idx, weight = _f32(grad_out), _i32(idx), _f32(weight)
+    b, c, n = grad_out.shape
+    grad = torch.empty((b, c, int(m)), dtype=torch.float32, device=grad_out.device)
+    wsb = lib.spx_three_interpolate_bwd_ws_bytes(b, m, n)
+    ws = workspace(grad_out.device, wsb)
+    check(lib.spx_three_interpolate_bwd(_ptr(grad_out), _ptr(idx), _ptr(weight), b, c, int(m), n, _ptr(grad), _ptr(ws), wsb,
+                                        _stream(grad_out)), "spx_three_interpolate_bwd")
+    return grad
