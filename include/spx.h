@@ -525,6 +525,49 @@ size_t spx_three_interpolate_bwd_ws_bytes(int32_t b, int64_t m, int64_t n);
 int spx_three_interpolate_bwd(const float *grad_out, const int32_t *idx, const float *weight, int32_t b, int32_t c,
                               int64_t m, int64_t n, float *grad_features, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 12. Points in boxes and RoI-aware pooling (the fork's point-head target assignment, PartA2-style RoI heads;
+ *     csrc/roiaware_pool3d.hip)
+ *    replaces: the roiaware_pool3d extension, reference pcdet/ops/roiaware_pool3d/src/roiaware_pool3d_kernel.cu, reached
+ *      from roiaware_pool3d_utils.py (point_head_template.py:119-126, loss_utils.py:602-612).
+ *    Boxes / RoIs are fp32 [.., 7] = (cx, cy, cz, dx, dy, dz, heading).  Inside test: |z - cz| > dz / 2 (in double)
+ *    rejects (a point on a z face is inside); then with (sx, sy) = (x - cx, y - cy), cosa = (float)cos(-(double)heading)
+ *    and sina likewise, local_x = (sx*cosa) + (sy*(-sina)) and local_y = (sx*sina) + (sy*cosa) in float without FMA
+ *    contraction, and the point is inside iff |local_x| < (double)dx / 2.0 + (double)1e-5f and the same for y.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* replaces: points_in_boxes_gpu (roiaware_pool3d_kernel.cu:290-335, python side roiaware_pool3d_utils.py:29-42).
+ *   pts [b, m, 3], boxes [b, t, 7] -> box_idx [b, m] = the first k (ascending) whose box contains the point, else -1.
+ *   Every element is written; t = 0 is legal (all -1).  Zero-padded boxes take part like any other box. */
+int spx_points_in_boxes(const float *pts, const float *boxes, int32_t b, int64_t m, int64_t t, int32_t *box_idx,
+                        spx_stream_t stream);
+
+/* replaces: roiaware_pool3d_cuda.forward (roiaware_pool3d_kernel.cu:41-227).  rois [n, 7], pts [np, 3], feats [np, c];
+ *   out size (ox, oy, oz), each in [1, 255]; max_pts >= 1 (each voxel keeps max_pts - 1 points); mode 0 = max, 1 = avg.
+ *   Cell of an in-box point: x_res = dx / ox, i = (int)((local_x + dx / 2) / x_res) in float (saturating, NaN -> 0),
+ *   taken as unsigned and clamped to ox - 1 (a negative index lands in the LAST cell); y, z likewise (local_z = z - cz).
+ *   Each voxel keeps the first max_pts - 1 in-box points in ascending point index.  Outputs, every element written:
+ *     pooled [n, ox, oy, oz, c]: max = the first maximum (strict >, from -inf) in point order, 0 when nothing beats -inf;
+ *       avg = (sum in point order from 0) / count, 0 when empty;
+ *     argmax [n, ox, oy, oz, c] (mode 0 only, NULL allowed for avg): point index of the maximum, -1 when none;
+ *     pt_cell [n, np]: cell (x*oy + y)*oz + z of point p in RoI r when the point is kept there, else -1;
+ *     vox_cnt [n, ox, oy, oz]: points kept per voxel.
+ *   pt_cell and vox_cnt are the record spx_roiaware_pool3d_bwd reads.  ws: spx_roiaware_pool3d_ws_bytes bytes. */
+size_t spx_roiaware_pool3d_ws_bytes(int64_t n, int64_t np, int32_t ox, int32_t oy, int32_t oz);
+int spx_roiaware_pool3d_fwd(const float *rois, const float *pts, const float *feats, int64_t n, int64_t np, int32_t c,
+                            int32_t ox, int32_t oy, int32_t oz, int32_t max_pts, int32_t mode, float *pooled,
+                            int32_t *argmax, int32_t *pt_cell, int32_t *vox_cnt, void *ws, size_t ws_bytes,
+                            spx_stream_t stream);
+
+/* replaces: roiaware_pool3d_cuda.backward (atomicAdd there, roiaware_pool3d_kernel.cu:230-287).  grad_out
+ *   [n, ox, oy, oz, c]; argmax (mode 0) / vox_cnt (mode 1) and pt_cell from the forward.  grad_in [np, c], fully written,
+ *   DETERMINISTIC: grad_in[p, ch] starts at 0.0f and adds the RoIs' contributions in ASCENDING RoI order r = 0, 1, ...;
+ *   RoI r contributes, for the voxel v = pt_cell[r, p] (none when -1), max: grad_out[r, v, ch] if argmax[r, v, ch] == p;
+ *   avg: grad_out[r, v, ch] * (1.0f / fmaxf((float)vox_cnt[r, v], 1.0f)), a float product. */
+int spx_roiaware_pool3d_bwd(const float *grad_out, const int32_t *argmax, const int32_t *pt_cell, const int32_t *vox_cnt,
+                            int64_t n, int64_t np, int32_t c, int32_t ox, int32_t oy, int32_t oz, int32_t mode,
+                            float *grad_in, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
-"""Axis-aligned 'nearest BEV' IoU used by the anchor target assigner
-(semantics of reference pcdet/utils/box_utils.py:249-298)."""
+"""Box helpers: the axis-aligned 'nearest BEV' IoU used by the anchor target assigner (semantics of reference
+pcdet/utils/box_utils.py:249-298), corners, range masks, and the point-head / gt-sampling helpers enlarge_box3d and
+remove_points_in_boxes3d."""
 import numpy as np
 import torch
 
@@ -52,3 +53,23 @@ def mask_boxes_outside_range_numpy(boxes, limit_range, min_num_corners=1):
     corners = boxes_to_corners_3d(np.asarray(boxes)[:, 0:7])
     inside = ((corners >= limit_range[0:3]) & (corners <= limit_range[3:6])).all(axis=2)
     return inside.sum(axis=1) >= min_num_corners
+
+
+def remove_points_in_boxes3d(points, boxes3d):
+    """Drop the points that lie in any box (reference box_utils.py:75-89, the host op's margin 1e-2).
+    points (num_points, 3 + C), boxes3d (N, 7) [x, y, z, dx, dy, dz, heading]; numpy in, numpy out."""
+    from ..ops.roiaware_pool3d import roiaware_pool3d_utils
+    boxes3d, is_numpy = common_utils.check_numpy_to_torch(boxes3d)
+    points, is_numpy = common_utils.check_numpy_to_torch(points)
+    point_masks = roiaware_pool3d_utils.points_in_boxes_cpu(points[:, 0:3], boxes3d)
+    points = points[point_masks.sum(dim=0) == 0]
+    return points.numpy() if is_numpy else points
+
+
+def enlarge_box3d(boxes3d, extra_width=(0, 0, 0)):
+    """Boxes with dx, dy, dz grown by extra_width (reference box_utils.py:145-158).  Returns a torch tensor, also for a
+    numpy input, as the reference does."""
+    boxes3d, is_numpy = common_utils.check_numpy_to_torch(boxes3d)
+    large_boxes3d = boxes3d.clone()
+    large_boxes3d[:, 3:6] += boxes3d.new_tensor(extra_width)[None, :]
+    return large_boxes3d

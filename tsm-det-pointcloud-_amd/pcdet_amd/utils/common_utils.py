@@ -8,6 +8,14 @@ import torch
 import torch.distributed as dist
 
 
+def check_numpy_to_torch(x):
+    """numpy array -> (float32 torch tensor sharing its memory, True); anything else -> (x, False)
+    (reference common_utils.py:21-24)."""
+    if isinstance(x, np.ndarray):
+        return torch.from_numpy(x).float(), True
+    return x, False
+
+
 def limit_period(val, offset=0.5, period=np.pi):
     """val - floor(val/period + offset) * period  (reference common_utils.py:27-30)."""
     is_np = isinstance(val, np.ndarray)

@@ -108,6 +108,12 @@ SIGNATURES = {
     "spx_three_interpolate": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, _vp, _vp]),
     "spx_three_interpolate_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, _i64]),
     "spx_three_interpolate_bwd": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "spx_points_in_boxes": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp]),
+    "spx_roiaware_pool3d_ws_bytes": (_sz, [_i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "spx_roiaware_pool3d_fwd": (_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_roiaware_pool3d_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
 }
 
 _lib = None

@@ -1039,3 +1039,53 @@ def three_interpolate_bwd(grad_out, idx, weight, m):
     check(lib.spx_three_interpolate_bwd(_ptr(grad_out), _ptr(idx), _ptr(weight), b, c, int(m), n, _ptr(grad), _ptr(ws), wsb,
                                         _stream(grad_out)), "spx_three_interpolate_bwd")
     return grad
+
+
+# ------------------------------------------------------------------------- points in boxes, RoI-aware pooling (§12)
+
+def points_in_boxes(points, boxes):
+    """spx_points_in_boxes: points (B, M, 3), boxes (B, T, 7) -> (B, M) int32, the first box holding each point or -1."""
+    _need_gpu(points, boxes)
+    lib = _lib.load()
+    points, boxes = _f32(points), _f32(boxes)
+    b, m, _ = points.shape
+    t = boxes.shape[1]
+    out = torch.empty((b, m), dtype=torch.int32, device=points.device)
+    check(lib.spx_points_in_boxes(_ptr(points), _ptr(boxes), b, m, t, _ptr(out), _stream(points)), "spx_points_in_boxes")
+    return out
+
+
+def roiaware_pool3d_fwd(rois, pts, feats, out_size, max_pts_each_voxel, pool_method):
+    """spx_roiaware_pool3d_fwd: rois (N, 7), pts (P, 3), feats (P, C), out_size (ox, oy, oz), pool_method 0 = max / 1 = avg
+    -> pooled (N, ox, oy, oz, C), argmax (same shape, int32; None for avg), pt_cell (N, P) and vox_cnt (N, ox, oy, oz)
+    int32 (the record the backward reads)."""
+    _need_gpu(rois, pts, feats)
+    lib = _lib.load()
+    rois, pts, feats = _f32(rois), _f32(pts), _f32(feats)
+    n, npt, c = rois.shape[0], pts.shape[0], feats.shape[1]
+    ox, oy, oz = (int(v) for v in out_size)
+    dev = feats.device
+    pooled = torch.empty((n, ox, oy, oz, c), dtype=torch.float32, device=dev)
+    argmax = torch.empty((n, ox, oy, oz, c), dtype=torch.int32, device=dev) if pool_method == 0 else None
+    pt_cell = torch.empty((n, npt), dtype=torch.int32, device=dev)
+    vox_cnt = torch.empty((n, ox, oy, oz), dtype=torch.int32, device=dev)
+    wsb = lib.spx_roiaware_pool3d_ws_bytes(n, npt, ox, oy, oz)
+    ws = workspace(dev, wsb)
+    check(lib.spx_roiaware_pool3d_fwd(_ptr(rois), _ptr(pts), _ptr(feats), n, npt, c, ox, oy, oz, int(max_pts_each_voxel),
+                                      int(pool_method), _ptr(pooled), _ptr(argmax), _ptr(pt_cell), _ptr(vox_cnt), _ptr(ws),
+                                      wsb, _stream(feats)), "spx_roiaware_pool3d_fwd")
+    return pooled, argmax, pt_cell, vox_cnt
+
+
+def roiaware_pool3d_bwd(grad_out, argmax, pt_cell, vox_cnt, pool_method):
+    """spx_roiaware_pool3d_bwd: grad_out (N, ox, oy, oz, C) -> grad_in (P, C), summed over RoIs in ascending order."""
+    _need_gpu(grad_out, argmax, pt_cell, vox_cnt)
+    lib = _lib.load()
+    grad_out = _f32(grad_out)
+    n, ox, oy, oz, c = grad_out.shape
+    npt = pt_cell.shape[1]
+    grad_in = torch.empty((npt, c), dtype=torch.float32, device=grad_out.device)
+    check(lib.spx_roiaware_pool3d_bwd(_ptr(grad_out), _ptr(None if argmax is None else _i32(argmax)), _ptr(_i32(pt_cell)),
+                                      _ptr(_i32(vox_cnt)), n, npt, c, ox, oy, oz, int(pool_method), _ptr(grad_in),
+                                      _stream(grad_out)), "spx_roiaware_pool3d_bwd")
+    return grad_in
