@@ -568,6 +568,37 @@ int spx_roiaware_pool3d_bwd(const float *grad_out, const int32_t *argmax, const 
                             int64_t n, int64_t np, int32_t c, int32_t ox, int32_t oy, int32_t oz, int32_t mode,
                             float *grad_in, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 13. Gather-project: a set-abstraction grouper's first 1x1 conv fused with the grouping that feeds it (the fork's
+ *     voxel-point SA modules; csrc/group_project.hip)
+ *    replaces: the grouped tensor (B, 3 + C, npoint, nsample) that the reference builds with grouping_operation, a
+ *      centre subtraction, torch.cat, empty-ball zeroing and a permute, followed by Conv2d(k=1) (pointnet2_modules.py,
+ *      _VoxelPointnetSAModuleFSDistillationBase.forward, point and voxel branches).
+ *    Queries m = bi * npoint + pi; slot s; source row r = idx[m, s] (GLOBAL rows, the caller adds frame offsets).
+ *    A column (m, s) is EMPTY when empty[m] != 0 (empty may be NULL: none) or r is outside [0, n_src).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* p [n_src, c_out] = F · Wf^T (the feature half of the conv, per source row; NULL: no feature term), wx [c_out, 3]
+ *   (NULL: no xyz term; at least one of p, wx), xyz [n_src, 3], ctr [b * npoint, 3], idx [b * npoint, nsample] int32,
+ *   empty [b * npoint] bytes.  y [b, c_out, npoint, nsample] (NCHW), every element written:
+ *     y[bi, o, pi, s] = empty column ? 0 : p[r, o] + ((wx[o,0]*(xyz[r,0]-ctr[m,0]) + wx[o,1]*(..1)) + wx[o,2]*(..2)).
+ *   The xyz term is evaluated relative to the centre (never folded into p). */
+int spx_group_project(const float *p, const float *wx, const float *xyz, const float *ctr, const int32_t *idx,
+                      const uint8_t *empty, int32_t c_out, int64_t n_src, int32_t b, int64_t npoint, int32_t nsample,
+                      float *y, spx_stream_t stream);
+
+/* Backward of spx_group_project.  dy [b, c_out, npoint, nsample].  Either output may be NULL (not computed):
+ *   dpt [c_out, n_src] (TRANSPOSED, fully written): dP^T[o, r] = sum of dy[.., o, ..] over the non-empty columns with
+ *     idx = r, DETERMINISTIC: columns stable-sorted by r, each run added in ascending column order (dF = dP · Wf and
+ *     dWf = dP^T · F are the caller's GEMMs);
+ *   dwx [c_out, 3]: sum over non-empty columns of dy * (xyz[r] - ctr[m]), DETERMINISTIC: fixed-order per-block partials
+ *     over chunks of 2048 columns, then a fixed-order sum of the partials.
+ *   No gradient flows to xyz or ctr.  ws: spx_group_project_bwd_ws_bytes bytes. */
+size_t spx_group_project_bwd_ws_bytes(int32_t c_out, int64_t n_src, int32_t b, int64_t npoint, int32_t nsample);
+int spx_group_project_bwd(const float *dy, const float *xyz, const float *ctr, const int32_t *idx, const uint8_t *empty,
+                          int32_t c_out, int64_t n_src, int32_t b, int64_t npoint, int32_t nsample, float *dpt,
+                          float *dwx, void *ws, size_t ws_bytes, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

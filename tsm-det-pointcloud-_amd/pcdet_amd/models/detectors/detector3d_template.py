@@ -66,7 +66,7 @@ class Detector3DTemplate(nn.Module):
     def build_backbone_3d(self, model_info_dict):
         if self.model_cfg.get('BACKBONE_3D', None) is None:
             return None, model_info_dict
-        m = backbones_3d.__all__[self.model_cfg.BACKBONE_3D.NAME](
+        m = backbones_3d.get_backbone_3d(self.model_cfg.BACKBONE_3D.NAME)(
             model_cfg=self.model_cfg.BACKBONE_3D, input_channels=model_info_dict['num_point_features'],
             grid_size=model_info_dict['grid_size'], voxel_size=model_info_dict['voxel_size'],
             point_cloud_range=model_info_dict['point_cloud_range'])

@@ -14,7 +14,7 @@ __all__ = [
     "calc_dist_matrix_for_sampling", "furthest_point_sample", "farthest_point_sample", "furthest_point_sample_matrix",
     "furthest_point_sample_weights", "furthest_point_sample_with_dist", "furthest_point_sample_with_weighted_dist",
     "gather_operation", "grouping_operation", "three_nn", "three_interpolate", "ball_query", "ball_query_dilated",
-    "QueryAndGroup", "QueryAndGroupDilated", "GroupAll",
+    "QueryAndGroup", "QueryAndGroupDilated", "GroupAll", "group_project",
 ]
 
 
@@ -185,3 +185,38 @@ class GroupAll(nn.Module):
             return grouped_xyz
         grouped_features = features.unsqueeze(2)
         return torch.cat([grouped_xyz, grouped_features], dim=1) if self.use_xyz else grouped_features
+
+
+class GroupProject(Function):
+    @staticmethod
+    def forward(ctx, features, wf, wx, xyz, ctr, idx, empty, batch):
+        """The first 1x1 conv of a grouper on the grouped tensor, without building it (spx.h §13):
+        features (N, C) source rows or None, wf (Cout, C) or None, wx (Cout, 3) or None, xyz (N, 3), ctr (B * npoint, 3),
+        idx (B * npoint, S) global rows, empty (B * npoint) bool or None -> (B, Cout, npoint, S)
+        = wf · features[idx] + wx · (xyz[idx] - ctr), 0 in empty balls."""
+        if (xyz is not None and xyz.requires_grad) or (ctr is not None and ctr.requires_grad):
+            raise RuntimeError("group_project: coordinates carry no gradient (they come from sampling); detach them")
+        p = torch.mm(features, wf.t()) if wf is not None else None
+        ctx.save_for_backward(features, wf, xyz, ctr, idx, empty)
+        ctx.has_wx = wx is not None
+        ctx.n_src = features.shape[0] if features is not None else xyz.shape[0]
+        return ops.group_project(p, wx, xyz, ctr, idx, empty, batch)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        features, wf, xyz, ctr, idx, empty = ctx.saved_tensors
+        need_f, need_wf, need_wx = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_dp = wf is not None and (need_f or need_wf)
+        need_dwx = ctx.has_wx and need_wx
+        if not (need_dp or need_dwx):
+            return (None,) * 8
+        dpt, dwx = ops.group_project_bwd(grad_out, xyz if need_dwx else None, ctr if need_dwx else None, idx, empty,
+                                         ctx.n_src, need_dp=need_dp, need_dwx=need_dwx)
+        d_f = torch.mm(dpt.t(), wf) if need_dp and need_f else None
+        d_wf = torch.mm(dpt, features) if need_dp and need_wf else None
+        return d_f, d_wf, dwx, None, None, None, None, None
+
+
+def group_project(features, wf, wx, xyz, ctr, idx, empty, batch):
+    """GroupProject.apply; see there."""
+    return GroupProject.apply(features, wf, wx, xyz, ctr, idx, empty, batch)

@@ -25,6 +25,28 @@ def get_overlapping_voxel_indices(point_coords, downsample_times, voxel_size, po
     return idx.long()
 
 
+def get_voxel_indices(point_coords, voxel_size, point_cloud_range):
+    """(N, 3) xyz -> (N, 3) int64 voxel index (x, y, z) = (xyz - range[0:3]) / voxel_size truncated toward zero, with no
+    range check (reference :48-83; voxel_size and point_cloud_range are tensors on the points' device)."""
+    assert point_coords.shape[1] == 3
+    return ((point_coords - point_cloud_range[0:3]) / voxel_size).long()
+
+
+class _CentroidMean(torch.autograd.Function):
+    """Gradient of the per-voxel mean: each point receives its voxel's gradient / the voxel's point count (a gather, so
+    deterministic); the forward values are the kernel's."""
+
+    @staticmethod
+    def forward(ctx, points, centroids, inverse, counts):
+        ctx.save_for_backward(inverse, counts)
+        return centroids.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        inverse, counts = ctx.saved_tensors
+        return grad[inverse] / counts[inverse].to(grad.dtype).unsqueeze(-1), None, None, None
+
+
 def get_centroid_per_voxel(points, voxel_idxs, num_points_in_voxel=None):
     """points (N, 4 + f) [bxyz + f], voxel_idxs (N, 4) non-negative ints -> centroids (N', 4 + f), their voxel indices
     (N', 4) in torch.unique(dim=0) order, rows merged per voxel (N', torch.unique's counts in both modes, as the
@@ -55,6 +77,9 @@ def get_centroid_per_voxel(points, voxel_idxs, num_points_in_voxel=None):
     else:
         centroids = means
     cells = out["coords"][:, [0, 3, 2, 1]].to(voxel_idxs.dtype)   # kernel returns (c0, c3, c2, c1)
+    if points.requires_grad and torch.is_grad_enabled():
+        assert num_points_in_voxel is None, "the weighted mean carries no gradient"
+        centroids = _CentroidMean.apply(points, centroids.to(points.dtype), inverse, counts)
     return centroids, cells, counts, inverse
 
 

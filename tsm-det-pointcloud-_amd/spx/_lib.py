@@ -114,6 +114,11 @@ SIGNATURES = {
                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spx_roiaware_pool3d_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    "spx_group_project": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _i64, ctypes.c_int32,
+                                 _vp, _vp]),
+    "spx_group_project_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, ctypes.c_int32, _i64, ctypes.c_int32]),
+    "spx_group_project_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _i64, ctypes.c_int32,
+                                     _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

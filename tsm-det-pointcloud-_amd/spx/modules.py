@@ -233,7 +233,10 @@ class SparseConvolution(SparseModule):
 
     def _rulebook(self, x):
         """Find (indice_key cache) or build the rulebook; returns (rulebook, out_indices, out_shape)."""
-        cached = x.find_indice_pair(self.indice_key)
+        # a 1x1x1 submanifold conv neither reads nor registers its indice_key (spconv 2.x computes it as a dense mm), so
+        # a later kernel-3 SubMConv3d may take over the same key (the fork's voxel-point SA U-Net does)
+        key_cached = not (self.subm and self.conv1x1)
+        cached = x.find_indice_pair(self.indice_key) if key_cached else None
         if cached is not None:
             _prebuild.wait_ready(cached)        # a table queued on the index stream (spx/prebuild.py)
         if self.inverse:
@@ -258,7 +261,7 @@ class SparseConvolution(SparseModule):
         else:
             rb = ops.conv_rulebook(x.indices, x.batch_size, x.spatial_shape, self.kernel_size, self.stride,
                                    self.padding, self.dilation)
-        if self.indice_key is not None:
+        if self.indice_key is not None and key_cached:
             x.indice_dict[self.indice_key] = rb
         return rb
 

@@ -539,6 +539,9 @@ def wgrad_counts_for(rb, pair, ld, kvol, n_out, d_n_out=None):
     return hit
 
 
+_WGRAD_MAX_C = 128      # spx_conv_wgrad's channel limit per side
+
+
 def conv_wgrad(feat_in, dout, pair, ld, n_out, wshape, d_n_out=None, counts=None):
     """d_n_out: optional device int64[1] live output-row count (n_out is then the capacity); counts: wgrad_counts of the
     table (computed inside the call when None)."""
@@ -553,6 +556,17 @@ def conv_wgrad(feat_in, dout, pair, ld, n_out, wshape, d_n_out=None, counts=None
     dw = torch.empty(tuple(wshape), dtype=torch.float32, device=dout.device)
     if feat_in.shape[0] == 0 or n_out == 0:
         return dw.zero_()
+    if cin > _WGRAD_MAX_C or cout > _WGRAD_MAX_C:
+        # the kernel takes up to 128 channels a side; dw[o, k, i] reads only feat_in[:, i] and dout[:, o], so wider
+        # layers (the voxel-point SA U-Net's 256) run as channel tiles with the same per-element arithmetic
+        for o0 in range(0, cout, _WGRAD_MAX_C):
+            o1 = min(o0 + _WGRAD_MAX_C, cout)
+            for i0 in range(0, cin, _WGRAD_MAX_C):
+                i1 = min(i0 + _WGRAD_MAX_C, cin)
+                dw[o0:o1, ..., i0:i1] = conv_wgrad(feat_in[:, i0:i1], dout[:, o0:o1], pair, ld, n_out,
+                                                   (o1 - o0,) + tuple(wshape[1:-1]) + (i1 - i0,), d_n_out=d_n_out,
+                                                   counts=counts)
+        return dw
     wsb = lib.spx_conv_wgrad_ws_bytes(cin, cout, K, n_out)
     ws = workspace(dout.device, wsb)
     check(lib.spx_conv_wgrad(_ptr(feat_in), cin, _ptr(dout), cout, K, _ptr(pair), ld, n_out, _ptr(d_n_out), _ptr(counts),
@@ -1089,3 +1103,49 @@ def roiaware_pool3d_bwd(grad_out, argmax, pt_cell, vox_cnt, pool_method):
                                       _ptr(_i32(vox_cnt)), n, npt, c, ox, oy, oz, int(pool_method), _ptr(grad_in),
                                       _stream(grad_out)), "spx_roiaware_pool3d_bwd")
     return grad_in
+
+
+# ------------------------------------------------------------------------- gather-project (§13)
+
+def group_project(p, wx, xyz, ctr, idx, empty, batch):
+    """spx_group_project: p (N, Cout) = F · Wf^T or None, wx (Cout, 3) or None, xyz (N, 3), ctr (B * npoint, 3),
+    idx (B * npoint, S) global source rows, empty (B * npoint) bool / uint8 or None -> y (B, Cout, npoint, S) with
+    y = p[idx] + wx · (xyz[idx] - ctr), 0 in empty balls."""
+    _need_gpu(p, wx, xyz, ctr, idx, empty)
+    lib = _lib.load()
+    ref = p if p is not None else wx
+    p = None if p is None else _f32(p)
+    wx = None if wx is None else _f32(wx)
+    xyz = None if xyz is None else _f32(xyz)
+    ctr = None if ctr is None else _f32(ctr)
+    idx = _i32(idx)
+    empty = None if empty is None else empty.detach().contiguous().to(torch.uint8)
+    c_out = p.shape[1] if p is not None else wx.shape[0]
+    n_src = p.shape[0] if p is not None else xyz.shape[0]
+    m, s = idx.shape
+    npoint = m // int(batch)
+    assert npoint * int(batch) == m
+    y = torch.empty((int(batch), c_out, npoint, s), dtype=torch.float32, device=ref.device)
+    check(lib.spx_group_project(_ptr(p), _ptr(wx), _ptr(xyz), _ptr(ctr), _ptr(idx), _ptr(empty), c_out, n_src, int(batch),
+                                npoint, s, _ptr(y), _stream(ref)), "spx_group_project")
+    return y
+
+
+def group_project_bwd(dy, xyz, ctr, idx, empty, n_src, need_dp=True, need_dwx=True):
+    """spx_group_project_bwd: dy (B, Cout, npoint, S) -> dP^T (Cout, n_src) or None, dWx (Cout, 3) or None, both summed
+    in a fixed order."""
+    _need_gpu(dy, xyz, ctr, idx, empty)
+    lib = _lib.load()
+    dy = _f32(dy)
+    b, c_out, npoint, s = dy.shape
+    xyz = None if xyz is None else _f32(xyz)
+    ctr = None if ctr is None else _f32(ctr)
+    idx = _i32(idx)
+    empty = None if empty is None else empty.detach().contiguous().to(torch.uint8)
+    dpt = torch.empty((c_out, int(n_src)), dtype=torch.float32, device=dy.device) if need_dp else None
+    dwx = torch.empty((c_out, 3), dtype=torch.float32, device=dy.device) if need_dwx else None
+    wsb = lib.spx_group_project_bwd_ws_bytes(c_out, int(n_src), b, npoint, s)
+    ws = workspace(dy.device, wsb)
+    check(lib.spx_group_project_bwd(_ptr(dy), _ptr(xyz), _ptr(ctr), _ptr(idx), _ptr(empty), c_out, int(n_src), b, npoint,
+                                    s, _ptr(dpt), _ptr(dwx), _ptr(ws), wsb, _stream(dy)), "spx_group_project_bwd")
+    return dpt, dwx
