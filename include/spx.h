@@ -599,6 +599,50 @@ int spx_group_project_bwd(const float *dy, const float *xyz, const float *ctr, c
                           int32_t c_out, int64_t n_src, int32_t b, int64_t npoint, int32_t nsample, float *dpt,
                           float *dwx, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 14. Point head: the eval tail of the fork's fast_cpc point head (PointHeadVoteSASAStatisticDistillation, student
+ *     branch; csrc/point_head.hip)
+ *    replaces: s_vote_layers + clamp + add (~8 launches), and after s_shared_fc_layer the per-class statistic-modulated
+ *      s_cls_block, s_reg_layers, permutes and the PointBinResidualCoder decode (~40 launches).
+ *    One workgroup owns a tile of 32 points; both 1x1-conv layers and the decode run from LDS in one launch, on the
+ *    VALU.  Inference only: no gradient is computed and the outputs carry no autograd history.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* One Conv1d(k=1, no bias) -> BatchNorm1d (eval affine) -> ReLU -> Conv1d(k=1, bias) stack, as DEVICE pointers to the
+ * module's own tensors (read at the call, passed to the kernel by value; nothing is folded or cached):
+ *   w1 [hidden, c_in]; bn_mean, bn_var, bn_weight, bn_bias [hidden]; bn_eps; w2 [c_out, hidden]; b2 [c_out].
+ *   hidden = ReLU((w1 . x - bn_mean) / sqrt(bn_var + bn_eps) * bn_weight + bn_bias), y = w2 . hidden + b2. */
+typedef struct spx_point_mlp {
+  const float *w1;
+  const float *bn_mean;
+  const float *bn_var;
+  const float *bn_weight;
+  const float *bn_bias;
+  float bn_eps;
+  const float *w2;
+  const float *b2;
+} spx_point_mlp;
+
+/* feat [b, c_in, n] (NCW), xyz [b, n, 3]; the candidates are the columns [lo, hi).  mlp: c_in -> hidden -> 3 (host
+ *   pointer to one descriptor), range: HOST float[3].  vote [b, hi - lo, 3], every element written:
+ *     vote = xyz[., lo + i] + min(max(offset, -range), range), NaN offsets propagating (torch.max / torch.min).
+ *   c_in <= 256 and hidden <= 128, else SPX_ERR_UNSUPPORTED. */
+int spx_point_vote(const float *feat, const float *xyz, int32_t b, int32_t c_in, int64_t n, int64_t lo, int64_t hi,
+                   const spx_point_mlp *mlp, int32_t hidden, const float *range, float *vote, spx_stream_t stream);
+
+/* feat [b, c, n] (after the shared FC), stat [num_class, c] (the teacher's object_statistic_features), vote_xyz
+ *   [b * n, 3]; cls: HOST array of num_class descriptors (c -> cls_hidden -> 1, applied to feat * stat[k]); reg: one
+ *   descriptor (c -> reg_hidden -> 6 + 2 * bins).  Points m = bi * n + i.  Every element written:
+ *     cls_out [b * n, num_class] logits; reg_out [b * n, 6 + 2 * bins] raw regression;
+ *     box_out [b * n, 7] = PointBinResidualCoder decode with use_mean_size False: xyz = reg[0:3] + vote_xyz,
+ *       sizes = expf(reg[3:6]), angle = ((float)bin + reg[6 + bins + bin]) * (float)(2 pi / bins) with bin the FIRST
+ *       maximum of reg[6 : 6 + bins] (torch.argmax: NaN counts as the maximum).
+ *   c <= 256, num_class <= 8, hidden widths <= 128, bins <= 32, else SPX_ERR_UNSUPPORTED. */
+int spx_point_head_predict(const float *feat, const float *stat, const float *vote_xyz, int32_t b, int32_t c, int64_t n,
+                           int32_t num_class, const spx_point_mlp *cls, int32_t cls_hidden, const spx_point_mlp *reg,
+                           int32_t reg_hidden, int32_t bins, float *cls_out, float *reg_out, float *box_out,
+                           spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

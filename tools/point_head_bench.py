@@ -1,0 +1,144 @@
+"""Times the fused point-head ops (include/spx.h §14) against the unfused torch transcription of the reference eval
+forward they replace, and the whole fast_cpc Point3DSSD eval forward split into its stages; writes one table to
+profiles/point_head_bench.log (and stdout).
+
+  python tools/point_head_bench.py [--iters N]
+
+Ops, at the KITTI (batch 16 x 512 candidates) and Waymo (batch 4 x 3072) shapes, random eval-mode weights:
+  vote: s_vote_layers (128 -> 128 -> 3) + clamp + add  vs  spx_point_vote;
+  tail: the three statistic-modulated class blocks, s_reg_layers (256 -> 128 -> 30), permutes and the two
+        PointBinResidualCoder decodes  vs  spx_point_head_predict.
+Detector: Point3DSSD built from the fast_cpc config (random init, eval, no_grad) on synthetic KITTI frames of 20 000
+points at batch 4 and 16: backbone, head VSA (vote + S_VSA_module + s_shared_fc_layer), head tail (fused predict +
+sigmoid), post-processing (per-class threshold + NMS), and the whole forward.  Times are microseconds per call, mean
+of --iters calls after one warm-up, CUDA events around the loop."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tsm-det-pointcloud-_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) * 1e3 / iters
+
+
+def frames(batch, n, seed=0):
+    from pcdet_amd.datasets import synthetic as syn
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(batch):
+        pts = syn.make_frame(1, i)["points"][:, :4]
+        out.append(pts[rng.choice(pts.shape[0], n, replace=pts.shape[0] < n)])
+    pts = np.stack(out).astype(np.float32)
+    bidx = np.repeat(np.arange(batch, dtype=np.float32), n)[:, None]
+    return torch.from_numpy(np.concatenate([bidx, pts.reshape(-1, 4)], 1)).cuda()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    args = ap.parse_args()
+    import __graft_entry__ as ge
+    ge.build(verbose=False)
+    import point_head_configs as phc
+    import point_head_ref as ref
+    from test_point_head_cpu import randomize
+    from pcdet_amd.models.dense_heads.point_head_vote_sasa_statistic_distillation import _mlp_params
+    from pcdet_amd.models.detectors import build_detector
+    from spx import ops
+
+    dev = torch.device("cuda:0")
+    it = args.iters
+    lines = ["device: %s" % torch.cuda.get_device_name(0), ""]
+    lines.append("%-34s %12s %12s %8s" % ("op (points)", "unfused us", "fused us", "speedup"))
+    torch.manual_seed(0)
+    for name, dataset, b, n in (("KITTI 16 x 512", "kitti", 16, 512), ("Waymo 4 x 3072", "waymo", 4, 3072)):
+        from pcdet_amd.models import dense_heads
+        head = dense_heads.__all__["PointHeadVoteSASAStatisticDistillation"](model_cfg=phc.head_cfg(dataset),
+                                                                             **phc.head_kwargs())
+        head = randomize(head, 1).to(dev).eval()
+        g = torch.Generator(dev).manual_seed(0)
+        coords = torch.cat([torch.arange(b, device=dev).repeat_interleave(n)[:, None].float(),
+                            torch.randn(b * n, 3, device=dev, generator=g) * 20], 1)
+        pf = torch.randn(b * n, 128, device=dev, generator=g)
+        feat = torch.relu(torch.randn(b, 256, n, device=dev, generator=g))
+        feat_ncw = pf.reshape(b, n, -1).permute(0, 2, 1).contiguous()
+        xyz = coords[:, 1:4].reshape(b, n, 3).contiguous()
+        lo, hi = head.model_cfg.SAMPLE_RANGE
+        with torch.no_grad():
+            vote = ops.point_vote(feat_ncw, xyz, lo, hi, _mlp_params(head.s_vote_layers),
+                                  head.s_vote_cfg.MAX_TRANSLATION_RANGE).view(-1, 3)
+            t_u = timed(lambda: ref.transcribe_vote(head, coords, pf, b), it)
+            t_f = timed(lambda: ops.point_vote(pf.reshape(b, n, -1).permute(0, 2, 1).contiguous(), xyz, lo, hi,
+                                               _mlp_params(head.s_vote_layers),
+                                               head.s_vote_cfg.MAX_TRANSLATION_RANGE), it)
+            lines.append("%-34s %12.1f %12.1f %7.1fx" % ("vote  " + name, t_u, t_f, t_u / t_f))
+            cls_p = [_mlp_params(m) for m in head.s_cls_block]
+            reg_p = _mlp_params(head.s_reg_layers)
+            t_u = timed(lambda: ref.transcribe_tail(head, feat, vote), it)
+            t_f = timed(lambda: ops.point_head_predict(feat, head.object_statistic_features, vote, cls_p, reg_p, 12),
+                        it)
+            lines.append("%-34s %12.1f %12.1f %7.1fx" % ("tail  " + name, t_u, t_f, t_u / t_f))
+
+    lines += ["", "%-34s %12s" % ("Point3DSSD eval, 20 000 pts/frame", "us")]
+    for b in (4, 16):
+        torch.manual_seed(0)
+        net = build_detector(phc.model_cfg(), 3, phc.dataset()).to(dev).eval()
+        head = net.point_head
+        pts = frames(b, 20000)
+        with torch.no_grad():
+            bd = net.backbone_3d({"batch_size": b, "points": pts.clone()})
+            out = head(dict(bd))
+            t_bb = timed(lambda: net.backbone_3d({"batch_size": b, "points": pts}), it)
+
+            def vsa():
+                coords = bd["s_point_coords"][:, 1:4].view(b, -1, 3).contiguous()
+                f = bd["s_point_features"].reshape(b, coords.size(1), -1).permute(0, 2, 1).contiguous()
+                v = ops.point_vote(f, coords, 0, 512, _mlp_params(head.s_vote_layers),
+                                   head.s_vote_cfg.MAX_TRANSLATION_RANGE)
+                _, x, _, _, _, _, _, _ = head.S_VSA_module(
+                    xyz=coords, new_xyz=v, features=bd["s_last_features"], sp_tensor=bd["s_last_sp_tensor"],
+                    centroids=bd["s_last_centroids"], centroid_voxel_idxs=bd["s_last_centroid_voxel_idxs"])
+                return head.s_shared_fc_layer(x), v
+
+            sfeat, v = vsa()
+            t_vsa = timed(vsa, it)
+            cls_p = [_mlp_params(m) for m in head.s_cls_block]
+            reg_p = _mlp_params(head.s_reg_layers)
+
+            def tail():
+                c, r, bx = ops.point_head_predict(sfeat, head.object_statistic_features, v.view(-1, 3), cls_p, reg_p,
+                                                  12)
+                return torch.sigmoid(c)
+
+            t_tail = timed(tail, it)
+            t_post = timed(lambda: net.post_processing(out), it)
+            t_all = timed(lambda: net({"batch_size": b, "points": pts}), it)
+        for label, t in (("backbone", t_bb), ("head VSA (vote + S_VSA + shared FC)", t_vsa),
+                         ("head tail (fused predict)", t_tail), ("post-processing", t_post),
+                         ("whole forward", t_all)):
+            lines.append("%-34s %12.1f" % ("b%-2d %s" % (b, label), t))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "point_head_bench.log"), "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,11 @@
 from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
+from .point_head_template import PointHeadTemplate
+from .point_head_vote_sasa_statistic_distillation import PointHeadVoteSASAStatisticDistillation
 
 __all__ = {
     'AnchorHeadTemplate': AnchorHeadTemplate,
     'AnchorHeadSingle': AnchorHeadSingle,
+    'PointHeadTemplate': PointHeadTemplate,
+    'PointHeadVoteSASAStatisticDistillation': PointHeadVoteSASAStatisticDistillation,
 }

@@ -1,9 +1,11 @@
 from .detector3d_template import Detector3DTemplate
+from .point_3dssd import Point3DSSD
 from .second_net import SECONDNet
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'SECONDNet': SECONDNet,
+    '3DSSD': Point3DSSD,
 }
 
 

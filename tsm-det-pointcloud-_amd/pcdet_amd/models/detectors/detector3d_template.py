@@ -5,7 +5,7 @@ Differences forced by the fork's drift, all backwards compatible
   * build_backbone_2d keeps `num_bev_features` from the module's own attribute (falls back to the fork's
     num_voxel_neck_features) and never overwrites num_point_features with None;
   * POST_PROCESSING.SCORE_THRESH may be a scalar (upstream) or a per-class list (fork's multi_thresh).
-Only the module slots of the SECOND path are populated; the other slots of `module_topology` stay None.
+Only the module slots of the SECOND and 3DSSD paths are populated; the other slots of `module_topology` stay None.
 """
 import os
 
@@ -124,7 +124,19 @@ class Detector3DTemplate(nn.Module):
         return self._absent('NECK', model_info_dict)
 
     def build_point_head(self, model_info_dict):
-        return self._absent('POINT_HEAD', model_info_dict)
+        if self.model_cfg.get('POINT_HEAD', None) is None:
+            return None, model_info_dict
+        if self.model_cfg.POINT_HEAD.get('USE_POINT_FEATURES_BEFORE_FUSION', False):
+            num_point_features = model_info_dict['num_point_features_before_fusion']
+        else:
+            num_point_features = model_info_dict['num_point_features']
+        m = dense_heads.__all__[self.model_cfg.POINT_HEAD.NAME](
+            model_cfg=self.model_cfg.POINT_HEAD, input_channels=num_point_features,
+            num_class=self.num_class if not self.model_cfg.POINT_HEAD.CLASS_AGNOSTIC else 1,
+            predict_boxes_when_training=self.model_cfg.get('ROI_HEAD', False),
+            voxel_size=model_info_dict.get('voxel_size', False), point_cloud_range=model_info_dict['point_cloud_range'])
+        model_info_dict['module_list'].append(m)
+        return m, model_info_dict
 
     def build_roi_head(self, model_info_dict):
         return self._absent('ROI_HEAD', model_info_dict)
@@ -138,8 +150,13 @@ class Detector3DTemplate(nn.Module):
         batch_size = batch_dict['batch_size']
         recall_dict, pred_dicts = {}, []
         for index in range(batch_size):
-            box_preds = batch_dict['batch_box_preds'][index]
-            cls_preds = batch_dict['batch_cls_preds'][index]
+            if batch_dict.get('batch_index', None) is not None:    # flat (N, .) predictions of a point head
+                assert batch_dict['batch_box_preds'].dim() == 2
+                batch_mask = (batch_dict['batch_index'] == index)
+            else:
+                batch_mask = index
+            box_preds = batch_dict['batch_box_preds'][batch_mask]
+            cls_preds = batch_dict['batch_cls_preds'][batch_mask]
             src_cls_preds = cls_preds
             assert cls_preds.shape[1] in [1, self.num_class]
             if not batch_dict['cls_preds_normalized']:

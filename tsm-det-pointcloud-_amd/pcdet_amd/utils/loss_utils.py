@@ -59,3 +59,33 @@ class WeightedSmoothL1Loss(nn.Module):
 class WeightedCrossEntropyLoss(nn.Module):
     def forward(self, input, target, weights):
         return F.cross_entropy(input.permute(0, 2, 1), target.argmax(dim=-1), reduction="none") * weights
+
+
+class WeightedBinaryCrossEntropyLoss(nn.Module):
+    """Constructed by the fast_cpc point head (reference loss_utils.py:339).  Holds no parameters or buffers; its
+    forward belongs to the point head's training path, which is not ported yet."""
+
+    def forward(self, input, target, weights):
+        raise NotImplementedError('WeightedBinaryCrossEntropyLoss.forward: point-head training is not ported')
+
+
+class PointSASALoss(nn.Module):
+    """Constructor of the reference's layer-wise SASA segmentation loss (loss_utils.py:545-569).  Holds no parameters
+    or buffers; target assignment and forward belong to the point head's training path, which is not ported yet."""
+
+    def __init__(self, func='BCE', layer_weights=None, extra_width=None, set_ignore_flag=False, num_class=None):
+        super().__init__()
+        self.layer_weights = layer_weights
+        if func == 'BCE':
+            self.loss_func = WeightedBinaryCrossEntropyLoss()
+        elif func == 'Focal':
+            self.loss_func = SigmoidFocalClassificationLoss()
+        else:
+            raise NotImplementedError
+        assert not set_ignore_flag or (set_ignore_flag and extra_width is not None)
+        self.extra_width = extra_width
+        self.set_ignore_flag = set_ignore_flag
+        self.num_class = num_class
+
+    def forward(self, l_points, l_scores, gt_boxes):
+        raise NotImplementedError('PointSASALoss.forward: point-head training is not ported')

@@ -24,6 +24,14 @@ _i32p = ctypes.POINTER(ctypes.c_int32)
 _f32p = ctypes.POINTER(ctypes.c_float)
 
 #: name -> (restype, argtypes).  Mirrors include/spx.h one to one (tests/test_abi.py checks the header).
+class PointMlp(ctypes.Structure):
+    """spx_point_mlp (include/spx.h §14): device pointers of one Conv1d -> BN -> ReLU -> Conv1d stack."""
+    _fields_ = [("w1", _vp), ("bn_mean", _vp), ("bn_var", _vp), ("bn_weight", _vp), ("bn_bias", _vp),
+                ("bn_eps", ctypes.c_float), ("w2", _vp), ("b2", _vp)]
+
+
+_mlpp = ctypes.POINTER(PointMlp)
+
 SIGNATURES = {
     "spx_strerror": (ctypes.c_char_p, [_int]),
     "spx_abi_version": (_int, []),
@@ -119,6 +127,10 @@ SIGNATURES = {
     "spx_group_project_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, ctypes.c_int32, _i64, ctypes.c_int32]),
     "spx_group_project_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _i64, ctypes.c_int32,
                                      _vp, _vp, _vp, _sz, _vp]),
+    "spx_point_vote": (_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _i64, _i64, _mlpp, ctypes.c_int32, _f32p,
+                              _vp, _vp]),
+    "spx_point_head_predict": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.c_int32, _mlpp,
+                                      ctypes.c_int32, _mlpp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1149,3 +1149,80 @@ def group_project_bwd(dy, xyz, ctr, idx, empty, n_src, need_dp=True, need_dwx=Tr
     check(lib.spx_group_project_bwd(_ptr(dy), _ptr(xyz), _ptr(ctr), _ptr(idx), _ptr(empty), c_out, int(n_src), b, npoint,
                                     s, _ptr(dpt), _ptr(dwx), _ptr(ws), wsb, _stream(dy)), "spx_group_project_bwd")
     return dpt, dwx
+
+
+# ------------------------------------------------------------------------------------------------ point head (§14)
+
+def _point_mlp(params, c_in, c_out, device):
+    """(w1 (H, c_in[, 1]), bn_mean, bn_var, bn_weight, bn_bias (H), eps, w2 (c_out, H[, 1]), b2 (c_out)) ->
+    (spx_point_mlp, H, tensors to keep alive through the launch).  The pointers are the tensors' own storage when they
+    are already contiguous float32 (a module's parameters are), so the kernel reads the current weights."""
+    w1, mean, var, gamma, beta, eps, w2, b2 = params
+    w1 = _f32(w1).reshape(w1.shape[0], -1)
+    w2 = _f32(w2).reshape(w2.shape[0], -1)
+    h = w1.shape[0]
+    vecs = [_f32(t).reshape(-1) for t in (mean, var, gamma, beta)]
+    b2 = _f32(b2).reshape(-1)
+    if w1.shape[1] != c_in or tuple(w2.shape) != (c_out, h) or b2.numel() != c_out or any(v.numel() != h for v in vecs):
+        raise _lib.SpxError("point-head MLP shapes do not chain: w1 %s, w2 %s, b2 %s, c_in %d, c_out %d"
+                            % (tuple(w1.shape), tuple(w2.shape), tuple(b2.shape), c_in, c_out))
+    keep = [w1] + vecs + [w2, b2]
+    _need_gpu(*keep)
+    if any(t.device != device for t in keep):
+        raise _lib.SpxError("point-head MLP parameters are on another device than the features")
+    desc = _lib.PointMlp(w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(),
+                         float(eps), w2.data_ptr(), b2.data_ptr())
+    return desc, h, keep
+
+
+def point_vote(feat, xyz, lo, hi, mlp, max_range):
+    """spx_point_vote: feat (B, C, N), xyz (B, N, 3), candidates are the columns [lo, hi) (clamped like a Python slice),
+    mlp = (w1, bn_mean, bn_var, bn_weight, bn_bias, eps, w2, b2) of the C -> H -> 3 vote layers, max_range 3 floats ->
+    vote (B, hi - lo, 3) = xyz[:, lo:hi] + clamp(offset, -max_range, max_range).  No autograd."""
+    _need_gpu(feat, xyz)
+    lib = _lib.load()
+    feat, xyz = _f32(feat), _f32(xyz)
+    b, c, n = feat.shape
+    if tuple(xyz.shape) != (b, n, 3):
+        raise _lib.SpxError("point_vote: xyz %s does not match features %s" % (tuple(xyz.shape), tuple(feat.shape)))
+    lo, hi, _ = slice(int(lo), int(hi)).indices(n)
+    hi = max(hi, lo)
+    desc, h, keep = _point_mlp(mlp, c, 3, feat.device)
+    vote = torch.empty((b, hi - lo, 3), dtype=torch.float32, device=feat.device)
+    check(lib.spx_point_vote(_ptr(feat), _ptr(xyz), b, c, n, lo, hi, ctypes.byref(desc), h, f_arr(max_range),
+                             _ptr(vote), _stream(feat)), "spx_point_vote")
+    return vote
+
+
+def point_head_predict(feat, stat, vote_xyz, cls_mlps, reg_mlp, bins):
+    """spx_point_head_predict: feat (B, C, N), stat (num_class, C), vote_xyz (B * N, 3), cls_mlps a list of num_class
+    (w1, bn_mean, bn_var, bn_weight, bn_bias, eps, w2, b2) tuples (C -> H -> 1, applied to feat * stat[k]), reg_mlp one
+    (C -> H -> 6 + 2 * bins) -> cls (B * N, num_class) logits, reg (B * N, 6 + 2 * bins), box (B * N, 7) decoded at the
+    vote xyz (PointBinResidualCoder, use_mean_size False).  No autograd."""
+    _need_gpu(feat, stat, vote_xyz)
+    lib = _lib.load()
+    feat, stat, vote_xyz = _f32(feat), _f32(stat), _f32(vote_xyz)
+    b, c, n = feat.shape
+    nc = len(cls_mlps)
+    if tuple(stat.shape) != (nc, c) or tuple(vote_xyz.shape) != (b * n, 3):
+        raise _lib.SpxError("point_head_predict: stat %s / vote_xyz %s do not match features %s and %d classes"
+                            % (tuple(stat.shape), tuple(vote_xyz.shape), tuple(feat.shape), nc))
+    descs, keep, hc = [], [], None
+    for p in cls_mlps:
+        d, h, k = _point_mlp(p, c, 1, feat.device)
+        if hc is not None and h != hc:
+            raise _lib.SpxError("point_head_predict: class blocks of different widths")
+        hc = h
+        descs.append(d)
+        keep += k
+    r_out = 6 + 2 * int(bins)
+    rdesc, hr, rkeep = _point_mlp(reg_mlp, c, r_out, feat.device)
+    cls_arr = (_lib.PointMlp * max(nc, 1))(*descs)
+    dev = feat.device
+    cls = torch.empty((b * n, nc), dtype=torch.float32, device=dev)
+    reg = torch.empty((b * n, r_out), dtype=torch.float32, device=dev)
+    box = torch.empty((b * n, 7), dtype=torch.float32, device=dev)
+    check(lib.spx_point_head_predict(_ptr(feat), _ptr(stat), _ptr(vote_xyz), b, c, n, nc, cls_arr, hc or 0,
+                                     ctypes.byref(rdesc), hr, int(bins), _ptr(cls), _ptr(reg), _ptr(box), _stream(feat)),
+          "spx_point_head_predict")
+    return cls, reg, box
