@@ -643,6 +643,48 @@ int spx_point_head_predict(const float *feat, const float *stat, const float *vo
                            int32_t reg_hidden, int32_t bins, float *cls_out, float *reg_out, float *box_out,
                            spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 15. Point-head post-processing without a host read (csrc/post_process.hip)
+ *    replaces: the per-frame, per-class mask / nonzero / topk / gather / NMS / count read of
+ *      Detector3DTemplate.post_processing with model_nms_utils.multi_thresh (fork) or class_agnostic_nms (upstream),
+ *      reference detector3d_template.py:207-349, and generate_recall_record (:501-542).
+ *    Two launches for the whole batch (one workgroup per frame and class, then one per frame), static capacity, the
+ *    live count stays on the device.  The pair test is the one of spx_nms_bev (csrc/box_iou.h).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Rows of the outputs per frame: min(n, n_thresh * post_max) per class, min(n, post_max) agnostic. */
+int64_t spx_point_post_process_capacity(int64_t n, int32_t n_thresh, int64_t post_max, int per_class);
+size_t spx_point_post_process_ws_bytes(int32_t b, int64_t n, int32_t n_thresh, int64_t post_max);
+
+/* scores [b * n] (already normalised), labels [b * n] int32 (1-based), boxes [b * n, 7]; frame f owns the rows
+ *   [f * n, (f + 1) * n).  thresholds: HOST float[n_thresh].  n <= 4096 else SPX_ERR_TOO_LARGE; n_thresh <= 8 else
+ *   SPX_ERR_UNSUPPORTED; pre_max, post_max >= 1.
+ * per_class != 0 (fork, n_thresh = number of classes), per frame, class c ascending:
+ *     members = rows with label == c + 1 and score >= thresholds[c], ordered by score descending, EQUAL SCORES LOWER ROW
+ *     FIRST; the first pre_max; greedy NMS (box j goes iff an earlier kept box i has iou(i, j) > nms_thresh; rotated BEV
+ *     IoU, or the axis-aligned one when axis_aligned != 0); the first post_max.  The classes' survivors together are
+ *     ordered again by the same rule and reduced by one more greedy NMS, with no limit.
+ * per_class == 0 (upstream, n_thresh = 1): score >= thresholds[0], order, pre_max, NMS, post_max.
+ * Outputs, K = the capacity above, EVERY element written on every call:
+ *     sel [b, K] int64 row in [0, b * n), -1 past the frame's count; count [b] int32;
+ *     out_boxes [b, K, 7], out_scores [b, K], out_labels [b, K] int64: the selected rows' values, 0 past the count.
+ * ws: spx_point_post_process_ws_bytes bytes. */
+int spx_point_post_process(const float *scores, const int32_t *labels, const float *boxes, int32_t b, int64_t n,
+                           const float *thresholds, int32_t n_thresh, float nms_thresh, int64_t pre_max, int64_t post_max,
+                           int axis_aligned, int per_class, int64_t *sel, int32_t *count, float *out_boxes,
+                           float *out_scores, int64_t *out_labels, void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* Recall record of the kept boxes (generate_recall_record, rcnn_* and gt): out_boxes [b, cap, 7] and count [b] as
+ *   written above, gt_boxes [b, g, gt_ld] (gt_ld >= 7, the first 7 columns are the box), thresholds: HOST
+ *   float[n_thresh], n_thresh <= 8.  The live gt rows of a frame are [0, k], k found by stepping back from row g - 1
+ *   while k > 0 and the row (all gt_ld columns, added in column order in fp32) sums to 0; a row of non-zero entries
+ *   that cancel to exactly 0 in one summation order and not in another may be counted differently from torch's sum.  recalled [b, n_thresh] int32 = live gt rows whose largest
+ *   3-D IoU (BEV overlap x height overlap / max(vol_a + vol_b - overlap, 1e-6)) over the frame's first count boxes is
+ *   > threshold, 0 with no kept box; num_gt [b] int32 = k + 1 (0 when g = 0). */
+int spx_recall_count(const float *out_boxes, const int32_t *count, int32_t b, int64_t cap, const float *gt_boxes, int64_t g,
+                     int32_t gt_ld, const float *thresholds, int32_t n_thresh, int32_t *recalled, int32_t *num_gt,
+                     spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

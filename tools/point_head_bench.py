@@ -11,7 +11,14 @@ Ops, at the KITTI (batch 16 x 512 candidates) and Waymo (batch 4 x 3072) shapes,
 Detector: Point3DSSD built from the fast_cpc config (random init, eval, no_grad) on synthetic KITTI frames of 20 000
 points at batch 4 and 16: backbone, head VSA (vote + S_VSA_module + s_shared_fc_layer), head tail (fused predict +
 sigmoid), post-processing (per-class threshold + NMS), and the whole forward.  Times are microseconds per call, mean
-of --iters calls after one warm-up, CUDA events around the loop."""
+of --iters calls after one warm-up, CUDA events around the loop.
+
+Post-processing (include/spx.h §15; also alone with --post-only), written to profiles/post_process_bench.log: the eager
+per-frame, per-class code (POST_PROCESSING.FUSED False) against the fused path (spx_point_post_process, one host read
+per batch) and against post_processing_static (no host read), at KITTI 4 x 512 and 16 x 512 and Waymo 4 x 3072 with each
+dataset's fast_cpc thresholds and NMS settings.  The inputs are the boxes the fused head tail decodes from random
+features at random vote positions; the logits are replaced by a permuted linspace(-3, 4), because a randomly initialised
+head scores every point near sigmoid(-4.6) and nothing would pass a KITTI threshold."""
 import argparse
 import os
 import sys
@@ -49,12 +56,83 @@ def frames(batch, n, seed=0):
     return torch.from_numpy(np.concatenate([bidx, pts.reshape(-1, 4)], 1)).cuda()
 
 
+def post_process_rows(it, log_name="post_process_bench.log"):
+    """The eager / fused / static post-processing table (see the module docstring)."""
+    import point_head_configs as phc
+    from test_point_head_cpu import randomize
+    from pcdet_amd.config import AttrDict
+    from pcdet_amd.models import dense_heads
+    from pcdet_amd.models.dense_heads.point_head_vote_sasa_statistic_distillation import _mlp_params
+    from pcdet_amd.models.detectors import build_detector
+    from spx import ops
+
+    dev = torch.device("cuda:0")
+    from spx import _lib
+    lines = ["device: %s" % torch.cuda.get_device_name(0), "library: %s" % os.path.relpath(_lib.LIB_PATH, ROOT), "",
+             "%-24s %10s %10s %10s %9s %9s %12s %8s" % ("post-processing", "eager us", "fused us", "static us", "eager/f",
+                                                        "eager/s", "kept/frame", "default")]
+    net = build_detector(phc.model_cfg(), 3, phc.dataset()).to(dev).eval()
+    slower = []
+    for name, dataset, b, n in (("KITTI 4 x 512", "kitti", 4, 512), ("KITTI 16 x 512", "kitti", 16, 512),
+                                ("Waymo 4 x 3072", "waymo", 4, 3072)):
+        torch.manual_seed(0)
+        head = dense_heads.__all__["PointHeadVoteSASAStatisticDistillation"](model_cfg=phc.head_cfg(dataset),
+                                                                             **phc.head_kwargs())
+        head = randomize(head, 1).to(dev).eval()
+        g = torch.Generator(dev).manual_seed(0)
+        feat = torch.relu(torch.randn(b, 256, n, device=dev, generator=g))
+        vote = torch.randn(b * n, 3, device=dev, generator=g) * 20
+        with torch.no_grad():
+            _, _, box = ops.point_head_predict(feat, head.object_statistic_features, vote,
+                                               [_mlp_params(m) for m in head.s_cls_block],
+                                               _mlp_params(head.s_reg_layers), 12)
+        cg = torch.Generator().manual_seed(1)
+        logits = torch.linspace(-3.0, 4.0, b * n * 3)[torch.randperm(b * n * 3, generator=cg)].view(b * n, 3).to(dev)
+        out = {"batch_size": b, "batch_index": torch.arange(b, device=dev).repeat_interleave(n).float(),
+               "batch_cls_preds": logits, "batch_box_preds": box, "cls_preds_normalized": False}
+        cfg = AttrDict(phc.post_processing_dict(dataset))
+        net.model_cfg.POST_PROCESSING = cfg
+        with torch.no_grad():
+            cfg["FUSED"] = False
+            want, _ = net.post_processing(dict(out))
+            t_e = timed(lambda: net.post_processing(dict(out)), it)
+            cfg["FUSED"] = True
+            got, _ = net.post_processing(dict(out))
+            t_f = timed(lambda: net.post_processing(dict(out)), it)
+            t_s = timed(lambda: net.post_processing_static(out), it)
+        for a, w in zip(got, want):
+            for k in ("pred_boxes", "pred_scores", "pred_labels"):
+                assert torch.equal(a[k], w[k]), (name, k)
+        kept = sum(p["pred_boxes"].shape[0] for p in got) / b
+        if t_f >= t_e:
+            slower.append(name)
+        default = "fused" if n <= net.FUSED_DEFAULT_MAX_N else "eager"
+        lines.append("%-24s %10.1f %10.1f %10.1f %8.1fx %8.1fx %12.1f %8s" % (name, t_e, t_f, t_s, t_e / t_f, t_e / t_s, kept,
+                                                                          default))
+    lines += ["", "fused = Detector3DTemplate.post_processing with the fused kernels and one host read of the counts;",
+              "static = post_processing_static, no host read.  pred_dicts of the fused and eager paths compared equal.",
+              "default = what post_processing does when POST_PROCESSING.FUSED is not set (FUSED: True was timed above).",
+              "fused NOT faster than eager at: %s" % (", ".join(slower) if slower else "no shape")]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", log_name), "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--post-only", action="store_true", help="only the post-processing table")
+    ap.add_argument("--post-log", default="post_process_bench.log",
+                    help="file name under profiles/ for the post-processing table (an A/B against a dev build of the "
+                         "library loaded through SPX_LIB_PATH gets its own)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build(verbose=False)
+    if args.post_only:
+        post_process_rows(args.iters, args.post_log)
+        return
     import point_head_configs as phc
     import point_head_ref as ref
     from test_point_head_cpu import randomize
@@ -138,6 +216,7 @@ def main():
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "point_head_bench.log"), "w") as f:
         f.write(text)
+    post_process_rows(it, args.post_log)
 
 
 if __name__ == "__main__":

@@ -131,6 +131,12 @@ SIGNATURES = {
                               _vp, _vp]),
     "spx_point_head_predict": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.c_int32, _mlpp,
                                       ctypes.c_int32, _mlpp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "spx_point_post_process_capacity": (_i64, [_i64, ctypes.c_int32, _i64, _int]),
+    "spx_point_post_process_ws_bytes": (_sz, [ctypes.c_int32, _i64, ctypes.c_int32, _i64]),
+    "spx_point_post_process": (_int, [_vp, _vp, _vp, ctypes.c_int32, _i64, _f32p, ctypes.c_int32, ctypes.c_float, _i64,
+                                      _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_recall_count": (_int, [_vp, _vp, ctypes.c_int32, _i64, _vp, _i64, ctypes.c_int32, _f32p, ctypes.c_int32, _vp,
+                                _vp, _vp]),
 }
 
 _lib = None

@@ -1226,3 +1226,70 @@ def point_head_predict(feat, stat, vote_xyz, cls_mlps, reg_mlp, bins):
                                      ctypes.byref(rdesc), hr, int(bins), _ptr(cls), _ptr(reg), _ptr(box), _stream(feat)),
           "spx_point_head_predict")
     return cls, reg, box
+
+
+# --------------------------------------------------------------------------------- point-head post-processing (§15)
+
+POST_PROCESS_MAX_N = 4096   # candidates per frame spx_point_post_process takes
+
+
+def point_post_process(scores, labels, boxes, batch_size, thresholds, nms_thresh, pre_max, post_max, axis_aligned=False,
+                       per_class=True):
+    """spx_point_post_process: scores (B * n) normalised, labels (B * n) 1-based, boxes (B * n, >= 7), frames contiguous
+    with n rows each; thresholds one float per class (per_class, the fork's multi_thresh) or a single one
+    (class-agnostic NMS) -> dict of static-capacity tensors, K rows per frame: sel (B, K) int64 rows of the input or
+    -1, count (B) int32, boxes (B, K, 7), scores (B, K), labels (B, K) int64, zeros past count.  No host read."""
+    _need_gpu(scores, labels, boxes)
+    lib = _lib.load()
+    b = int(batch_size)
+    thresholds = [float(t) for t in (thresholds if isinstance(thresholds, (list, tuple)) else [thresholds])]
+    if scores.dim() != 1 or labels.shape != scores.shape or boxes.dim() != 2 or boxes.shape[0] != scores.shape[0] \
+            or boxes.shape[1] < 7 or b < 0 or (b == 0 and scores.shape[0] != 0) or (b > 0 and scores.shape[0] % b != 0):
+        raise _lib.SpxError("point_post_process: scores %s, labels %s, boxes %s do not make %d equal frames of (n, 7) boxes"
+                            % (tuple(scores.shape), tuple(labels.shape), tuple(boxes.shape), b))
+    if not per_class and len(thresholds) != 1:
+        raise _lib.SpxError("point_post_process: class-agnostic mode takes one threshold, got %d" % len(thresholds))
+    n = scores.shape[0] // b if b > 0 else 0
+    dev = scores.device
+    scores, labels, boxes = _f32(scores), _i32(labels), _f32(boxes[:, :7])
+    nt = len(thresholds)
+    k = int(lib.spx_point_post_process_capacity(n, nt, int(post_max), int(bool(per_class)))) if nt > 0 else 0
+    out = {"sel": torch.empty((b, k), dtype=torch.int64, device=dev),
+           "count": torch.empty((b,), dtype=torch.int32, device=dev),
+           "boxes": torch.empty((b, k, 7), dtype=torch.float32, device=dev),
+           "scores": torch.empty((b, k), dtype=torch.float32, device=dev),
+           "labels": torch.empty((b, k), dtype=torch.int64, device=dev)}
+    if b * k == 0 and nt > 0 and int(post_max) >= 1:
+        out["count"].zero_()      # frames without candidates: nothing to launch (and no storage to point at)
+        return out
+    wsb = lib.spx_point_post_process_ws_bytes(b, n, nt, int(post_max))
+    ws = workspace(dev, wsb)
+    check(lib.spx_point_post_process(_ptr(scores), _ptr(labels), _ptr(boxes), b, n, f_arr(thresholds), nt, float(nms_thresh),
+                                     int(pre_max), int(post_max), int(bool(axis_aligned)), int(bool(per_class)),
+                                     _ptr(out["sel"]), _ptr(out["count"]), _ptr(out["boxes"]), _ptr(out["scores"]),
+                                     _ptr(out["labels"]), _ptr(ws), wsb, _stream(scores)), "spx_point_post_process")
+    return out
+
+
+def recall_count(out_boxes, count, gt_boxes, thresholds):
+    """spx_recall_count: out_boxes (B, K, 7) and count (B) int32 of point_post_process, gt_boxes (B, G, >= 7) padded with
+    trailing zero rows, thresholds a list of floats -> recalled (B, T) int32, num_gt (B) int32 (the reference's
+    generate_recall_record, rcnn_* and gt, per frame).  No host read."""
+    _need_gpu(out_boxes, count, gt_boxes)
+    lib = _lib.load()
+    thresholds = [float(t) for t in thresholds]
+    if out_boxes.dim() != 3 or out_boxes.shape[2] != 7 or count.dim() != 1 or count.shape[0] != out_boxes.shape[0] \
+            or gt_boxes.dim() != 3 or gt_boxes.shape[0] != out_boxes.shape[0] or gt_boxes.shape[2] < 7 \
+            or count.dtype != torch.int32:
+        raise _lib.SpxError("recall_count: out_boxes %s, count %s (%s), gt_boxes %s do not match"
+                            % (tuple(out_boxes.shape), tuple(count.shape), count.dtype, tuple(gt_boxes.shape)))
+    out_boxes, gt_boxes, count = _f32(out_boxes), _f32(gt_boxes), count.contiguous()
+    b, k, _ = out_boxes.shape
+    nt = len(thresholds)
+    dev = out_boxes.device
+    recalled = torch.empty((b, nt), dtype=torch.int32, device=dev)
+    num_gt = torch.empty((b,), dtype=torch.int32, device=dev)
+    check(lib.spx_recall_count(_ptr(out_boxes), _ptr(count), b, k, _ptr(gt_boxes), gt_boxes.shape[1], gt_boxes.shape[2],
+                               f_arr(thresholds), nt, _ptr(recalled), _ptr(num_gt), _stream(out_boxes)),
+          "spx_recall_count")
+    return recalled, num_gt
