@@ -685,6 +685,36 @@ int spx_recall_count(const float *out_boxes, const int32_t *count, int32_t b, in
                      int32_t gt_ld, const float *thresholds, int32_t n_thresh, int32_t *recalled, int32_t *num_gt,
                      spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 16. Point-head target assignment without a host read (csrc/point_targets.hip)
+ *    replaces: the per-frame loops of the fork's point head and SASA loss (assign_stack_targets_mask,
+ *      assign_stack_targets_simple, PointSASALoss.assign_target, generate_centerness_label): points_in_boxes_gpu once
+ *      or twice per frame, boolean-mask indexing with its count reads, PointBinResidualCoder.encode_torch on the
+ *      compacted rows and a scatter back.
+ *    One launch for the whole batch, outputs of the static shape b * n, deterministic (no atomics).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* points [b, n, 3]; gt_boxes [b, m, ld], ld >= 8, columns [x, y, z, dx, dy, dz, rz, class, ...] (zero-padded rows are
+ *   scanned like any other box; may be NULL when m == 0); extra_width: HOST float[3], added to (dx, dy, dz) in float to
+ *   make the enlarged boxes.  The inside test is the one of spx_points_in_boxes.
+ * mode 0 (plain): hit = the first enlarged box holding the point; label = class(hit), 0 without a hit.
+ * mode 1 (ignore ring): hit = the first gt box holding the point; label = class(hit); without a hit -1 when some
+ *   enlarged box holds the point, else 0.
+ * mode 2 (ball): hit = the first gt box holding the point; label = class(hit) when ||centre(hit) - point|| <
+ *   central_radius (float, strict), else -1; 0 without a hit.
+ * class(k) = 1 when num_class == 1, else (int64)gt_boxes[k][7].  A point is foreground when its label is > 0.
+ * angle_bin_num 0: no regression code; 1..32, else SPX_ERR_UNSUPPORTED; mode outside 0..2: SPX_ERR_UNSUPPORTED.
+ * Outputs, rows r = frame * n + point, EVERY element written; the float outputs may be NULL (skipped):
+ *   cls_labels [b * n] int64; box_idx [b * n] int32 = hit or -1;
+ *   box_labels [b * n, 7] = the hit's box as stored (not enlarged), center_labels [b * n, 3] = its xyz,
+ *   reg_labels [b * n, 6 + 2 * angle_bin_num] = PointBinResidualCoder.encode_torch (use_mean_size False) of the hit's
+ *     box against the point as torch evaluates it on the CPU in float, centerness [b * n] =
+ *     generate_centerness_label with the point as point_base: all zero for points that are not foreground. */
+int spx_point_assign_targets(const float *points, const float *gt_boxes, int32_t b, int64_t n, int64_t m, int32_t ld,
+                             const float *extra_width, int32_t mode, float central_radius, int32_t num_class,
+                             int32_t angle_bin_num, int64_t *cls_labels, int32_t *box_idx, float *box_labels,
+                             float *center_labels, float *reg_labels, float *centerness, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,42 +24,14 @@
 
 #pragma clang fp contract(off)
 
+#include "box_inside.h"   // BoxC, box_consts, in_box: after the pragma, which covers them
+
 namespace {
 
 constexpr int kPibThreads = 256;     // points_in_boxes: points per workgroup = boxes staged per LDS chunk
 constexpr int kColThreads = 1024;    // collection: one workgroup per RoI
 constexpr int kColWaves = kColThreads / SPX_WAVE;
 constexpr int kLdsCells = 8192;      // voxel counters live in LDS up to this many cells per RoI, else in vox_cnt
-constexpr float kGpuMargin = 1e-5f;
-
-struct BoxC {            // per-box constants of the inside test
-  float cx, cy, cz, cosa, sina, pad0;
-  double hz, lx, ly;     // dz / 2, dx / 2 + margin, dy / 2 + margin (all in double, as the reference compares)
-};
-
-__device__ __forceinline__ BoxC box_consts(const float* bx) {
-  BoxC c;
-  c.cx = bx[0];
-  c.cy = bx[1];
-  c.cz = bx[2];
-  const float rz = bx[6];
-  c.cosa = (float)cos((double)(-rz));
-  c.sina = (float)sin((double)(-rz));
-  c.pad0 = 0.f;
-  c.hz = (double)bx[5] / 2.0;
-  c.lx = (double)bx[3] / 2.0 + (double)kGpuMargin;
-  c.ly = (double)bx[4] / 2.0 + (double)kGpuMargin;
-  return c;
-}
-
-// the reference's check_pt_in_box3d; local_x / local_y are written only when the z test passes
-__device__ __forceinline__ bool in_box(const BoxC& b, float x, float y, float z, float& lx, float& ly) {
-  if ((double)fabsf(z - b.cz) > b.hz) return false;
-  const float sx = x - b.cx, sy = y - b.cy;
-  lx = sx * b.cosa + sy * (-b.sina);   // contraction is off for this file
-  ly = sx * b.sina + sy * b.cosa;
-  return (double)fabsf(lx) < b.lx && (double)fabsf(ly) < b.ly;
-}
 
 // float -> int as the hardware convert does it: saturating, NaN -> 0
 __device__ __forceinline__ int f2i_sat(float f) {

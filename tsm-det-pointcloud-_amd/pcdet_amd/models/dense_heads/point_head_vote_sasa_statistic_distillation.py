@@ -6,8 +6,12 @@ init_weights), so state_dict keys and shapes equal the reference's and fork chec
 ported: the student branch with self.training False (reference forward, lines 1013-1295).  Its vote step and its tail
 after s_shared_fc_layer run as two HIP ops (csrc/point_head.hip, include/spx.h §14) that read the modules' own
 parameters at every call; the S_VSA_module and s_shared_fc_layer are the existing fused SA path and a GEMM.  The ops
-compute no gradient, so the head's outputs carry no autograd history.  Training (teacher forward, target assignment,
-the losses, SASA, statistic momentum) raises NotImplementedError.
+compute no gradient, so the head's outputs carry no autograd history.
+
+Training is still NOT ported: forward in train mode and get_loss raise NotImplementedError (the teacher forward, the
+losses, SASA's loss_forward and the statistic momentum update are missing).  What training will consume is here: the
+target assignment, assign_targets_simple / assign_targets / assign_stu_targets, each one HIP launch for the whole
+batch with no host read (point_targets.py, csrc/point_targets.hip, include/spx.h §16).  forward does not call them yet.
 """
 import numpy as np
 import torch
@@ -17,6 +21,7 @@ from spx import ops as spx_ops
 
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...utils import box_coder_utils, loss_utils
+from . import point_targets
 from .point_head_template import PointHeadTemplate
 
 
@@ -189,10 +194,34 @@ class PointHeadVoteSASAStatisticDistillation(PointHeadTemplate):
         fc_layers.append(nn.Conv1d(pre_channel, output_channels, kernel_size=1, bias=True))
         return nn.Sequential(*fc_layers)
 
+    def assign_targets_simple(self, points, gt_boxes, extra_width=None, set_ignore_flag=True):
+        """The vote targets.  points (N1 + N2 + ..., 4) [bs_idx, x, y, z], gt_boxes (B, M, 8) -> point_cls_labels,
+        point_reg_labels (., 3)."""
+        return point_targets.assign_targets_simple(points, gt_boxes, extra_width=extra_width,
+                                                   set_ignore_flag=set_ignore_flag)
+
+    def _assign_mask_targets(self, points, gt_boxes):
+        target_cfg = self.model_cfg.TARGET_CONFIG
+        if target_cfg.ASSIGN_METHOD != 'mask':
+            raise NotImplementedError('ASSIGN_METHOD %s is not ported (the fast_cpc configs use mask)'
+                                      % target_cfg.ASSIGN_METHOD)
+        return point_targets.assign_stack_targets_mask(points, gt_boxes, self.box_coder, self.num_class,
+                                                       central_radius=target_cfg.get('GT_CENTRAL_RADIUS', 2.0))
+
+    def assign_targets(self, input_dict):
+        """The teacher's targets on point_vote_coords (N1 + N2 + ..., 4) against gt_boxes (B, M, 8) ->
+        point_cls_labels, point_reg_labels (., code_size), point_box_labels (., 7)."""
+        return self._assign_mask_targets(input_dict['point_vote_coords'], input_dict['gt_boxes'])
+
+    def assign_stu_targets(self, input_dict):
+        """The student's targets: the same on s_point_vote_coords."""
+        return self._assign_mask_targets(input_dict['s_point_vote_coords'], input_dict['gt_boxes'])
+
     def get_loss(self, tb_dict=None):
         raise NotImplementedError('PointHeadVoteSASAStatisticDistillation: training is not ported (needs the teacher '
-                                  'forward, assign_targets / assign_stu_targets, the vote, cls, box, corner, iou and '
-                                  'SASA losses and the statistic momentum update)')
+                                  'forward, the vote, cls, box, corner, iou and SASA losses and the statistic momentum '
+                                  'update; their targets are assign_targets_simple / assign_targets / '
+                                  'assign_stu_targets)')
 
     def forward(self, batch_dict):
         """Eval forward of the student branch.

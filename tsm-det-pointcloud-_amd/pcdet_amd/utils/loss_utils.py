@@ -70,8 +70,9 @@ class WeightedBinaryCrossEntropyLoss(nn.Module):
 
 
 class PointSASALoss(nn.Module):
-    """Constructor of the reference's layer-wise SASA segmentation loss (loss_utils.py:545-569).  Holds no parameters
-    or buffers; target assignment and forward belong to the point head's training path, which is not ported yet."""
+    """The reference's layer-wise SASA segmentation loss (loss_utils.py:545-704) up to its targets: the constructor
+    (no parameters or buffers), assign_target and forward, which assigns the targets of every weighted layer, one HIP
+    launch per layer for the whole batch and no host read.  loss_forward, the loss itself, is not ported yet."""
 
     def __init__(self, func='BCE', layer_weights=None, extra_width=None, set_ignore_flag=False, num_class=None):
         super().__init__()
@@ -87,5 +88,24 @@ class PointSASALoss(nn.Module):
         self.set_ignore_flag = set_ignore_flag
         self.num_class = num_class
 
+    def assign_target(self, points, gt_boxes):
+        """points (N1 + N2 + ..., 4) [bs_idx, x, y, z], gt_boxes (B, M, 8) -> point_cls_labels (.) long (0 background,
+        -1 ignored), point_box_labels (., 7), point_part_labels (., 3)."""
+        from ..models.dense_heads import point_targets
+        return point_targets.sasa_assign_target(points, gt_boxes, extra_width=self.extra_width,
+                                                set_ignore_flag=self.set_ignore_flag, num_class=self.num_class)
+
     def forward(self, l_points, l_scores, gt_boxes):
-        raise NotImplementedError('PointSASALoss.forward: point-head training is not ported')
+        """l_points: per layer (N, 4) [bs_idx, x, y, z]; l_scores: per layer (N, 1) or None; gt_boxes (B, M, 8) ->
+        l_labels, l_boxes, l_parts.  As in the reference, a layer without scores or with weight 0 appends None to
+        l_labels only."""
+        l_labels, l_boxes, l_parts = [], [], []
+        for i in range(len(self.layer_weights)):
+            if l_scores[i] is None or self.layer_weights[i] == 0:
+                l_labels.append(None)
+                continue
+            li_labels, li_boxes, li_parts = self.assign_target(l_points[i], gt_boxes)
+            l_labels.append(li_labels)
+            l_boxes.append(li_boxes)
+            l_parts.append(li_parts)
+        return l_labels, l_boxes, l_parts

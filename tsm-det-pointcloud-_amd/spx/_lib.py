@@ -137,6 +137,9 @@ SIGNATURES = {
                                       _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spx_recall_count": (_int, [_vp, _vp, ctypes.c_int32, _i64, _vp, _i64, ctypes.c_int32, _f32p, ctypes.c_int32, _vp,
                                 _vp, _vp]),
+    "spx_point_assign_targets": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _f32p, ctypes.c_int32,
+                                        ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
 }
 
 _lib = None

@@ -1293,3 +1293,55 @@ def recall_count(out_boxes, count, gt_boxes, thresholds):
                                f_arr(thresholds), nt, _ptr(recalled), _ptr(num_gt), _stream(out_boxes)),
           "spx_recall_count")
     return recalled, num_gt
+
+
+# ------------------------------------------------------------------------------ point-head target assignment (§16)
+
+TARGET_PLAIN, TARGET_IGNORE_RING, TARGET_BALL = 0, 1, 2
+_TARGET_FLOAT_OUTPUTS = ("box_labels", "center_labels", "reg_labels", "centerness")
+
+
+def point_assign_targets(points, gt_boxes, mode, extra_width=None, central_radius=0.0, num_class=1, angle_bin_num=0,
+                         want=_TARGET_FLOAT_OUTPUTS):
+    """spx_point_assign_targets: points (B, N, 3), gt_boxes (B, M, >= 8) [x, y, z, dx, dy, dz, rz, class, ...], mode
+    TARGET_PLAIN (foreground = inside the box grown by extra_width), TARGET_IGNORE_RING (foreground = inside the gt box,
+    -1 in the grown-only ring) or TARGET_BALL (foreground = inside the gt box and within central_radius of its centre,
+    -1 for the rest of the box) -> dict of static-shape tensors over the B * N points, frame-major: cls_labels int64,
+    box_idx int32 (first box holding the point, -1 none) and those of `want`: box_labels (., 7), center_labels (., 3),
+    reg_labels (., 6 + 2 * angle_bin_num; needs angle_bin_num > 0), centerness (.), zero for points whose label is not
+    > 0.  num_class 1 labels every foreground point 1; any other value, None included, takes (int64) of the class
+    column.  One launch, no host read, no data-dependent shape."""
+    _need_gpu(points, gt_boxes)
+    lib = _lib.load()
+    if points.dim() != 3 or points.shape[2] != 3 or gt_boxes.dim() != 3 or gt_boxes.shape[0] != points.shape[0] \
+            or gt_boxes.shape[2] < 8:
+        raise _lib.SpxError("point_assign_targets: points %s and gt_boxes %s are not (B, N, 3) and (B, M, >= 8)"
+                            % (tuple(points.shape), tuple(gt_boxes.shape)))
+    want = tuple(want)
+    unknown = [k for k in want if k not in _TARGET_FLOAT_OUTPUTS]
+    if unknown or ("reg_labels" in want and int(angle_bin_num) <= 0):
+        raise _lib.SpxError("point_assign_targets: want %s (reg_labels needs angle_bin_num > 0, got %d)"
+                            % (want, int(angle_bin_num)))
+    points, gt_boxes = _f32(points), _f32(gt_boxes)
+    b, n, _ = points.shape
+    m, ld = gt_boxes.shape[1], gt_boxes.shape[2]
+    dev = points.device
+    rows = b * n
+    widths = {"box_labels": (rows, 7), "center_labels": (rows, 3), "reg_labels": (rows, 6 + 2 * int(angle_bin_num)),
+              "centerness": (rows,)}
+    out = {"cls_labels": torch.empty((rows,), dtype=torch.int64, device=dev),
+           "box_idx": torch.empty((rows,), dtype=torch.int32, device=dev)}
+    for k in want:
+        out[k] = torch.empty(widths[k], dtype=torch.float32, device=dev)
+    num_class = 0 if num_class is None else int(num_class)      # the library tests num_class == 1 only
+    ew = f_arr([0.0, 0.0, 0.0] if extra_width is None else [float(v) for v in extra_width])
+    if len(ew) != 3:
+        raise _lib.SpxError("point_assign_targets: extra_width takes 3 values, got %d" % len(ew))
+    if rows == 0:
+        return out
+    check(lib.spx_point_assign_targets(_ptr(points), _ptr(gt_boxes) if m > 0 else None, b, n, m, ld, ew, int(mode),
+                                       float(central_radius), num_class, int(angle_bin_num),
+                                       _ptr(out["cls_labels"]), _ptr(out["box_idx"]), _ptr(out.get("box_labels")),
+                                       _ptr(out.get("center_labels")), _ptr(out.get("reg_labels")),
+                                       _ptr(out.get("centerness")), _stream(points)), "spx_point_assign_targets")
+    return out
