@@ -715,6 +715,63 @@ int spx_point_assign_targets(const float *points, const float *gt_boxes, int32_t
                              int32_t angle_bin_num, int64_t *cls_labels, int32_t *box_idx, float *box_labels,
                              float *center_labels, float *reg_labels, float *centerness, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 17. Point-head losses, forward + gradient in one pass, without a host read (csrc/point_loss.hip)
+ *    replaces: PointHeadVoteSASAStatisticDistillation.get_vote_layer_loss / get_cls_layer_loss / get_box_layer_loss with
+ *      generate_centerness_label, get_rdiou and get_corner_loss_lidar, normalised as get_loss does, and their autograd
+ *      (reference pcdet/models/dense_heads/point_head_vote_sasa_statistic_distillation.py:570-1011, with
+ *      WeightedSmoothL1Loss without code weights and WeightedBinaryCrossEntropyLoss, pcdet/utils/loss_utils.py:141-203,
+ *      339-362), and PointSASALoss.loss_forward (loss_utils.py:706-753).
+ *    Three launches per call (normaliser counts, one thread per row with a partial sum per block, a fixed-order sum of
+ *    the partials); no float atomics, so the results are bitwise reproducible; a batch without positives takes the same
+ *    path.  Where the reference takes min / max of equal operands the first one gets the gradient (torch halves it).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Rows r = frame * n_per_frame + point, n rows in all; all device fp32 unless noted.
+ *   student (the gradients are w.r.t. these): vote_coords [n, 3], cls_preds [n, C] logits, reg_preds [n, 6 + 2K],
+ *     box_preds [n, 7]; teacher, constants: t_cls_preds [n, C], t_reg_preds [n, 6 + 2K] (columns 0..5 are read),
+ *     t_box_preds [n, 7]; targets: vote_cls_labels [n] int64 (> 0: vote positive), vote_reg_labels [n, 3],
+ *     cls_labels [n] int64 (> 0 foreground = class, 0 background, -1 ignored), reg_labels [n, 6 + 2K] (PointBinResidualCoder
+ *     code, use_mean_size False), box_labels [n, 7].  C = num_class <= 8, K = angle_bin_num <= 32, else
+ *     SPX_ERR_UNSUPPORTED.
+ *   params: HOST float[11] = LOSS_WEIGHTS (vote_reg, point_cls, point_offset_reg, point_angle_cls, point_angle_reg,
+ *     point_similarity (not read), point_iou, point_corner), smooth-L1 beta (< 1e-5: L1), centerness_min, centerness_max.
+ *   with_centerness: the cls target of a positive's class column is cmin + (cmax - cmin) * (centerness * rdiou + 1e-8)^(1/4)
+ *     (centerness of vote_coords in box_labels, no gradient; rdiou of box_preds against box_labels, WITH gradient into
+ *     box_preds), else 1.  rdiou / corner: RDIOU_REGRESS_REGULARIZATION / CORNER_LOSS_REGULARIZATION.
+ *   vote = w * sum over vote positives of smoothL1(vote_coords - vote_reg_labels) / max(#vote positives, 1)
+ *   cls  = w * sum over rows with label >= 0 of mean_c [0.5 BCE(x, target) + 0.5 BCE(x / 3, sigmoid(t / 3))]
+ *          / max(#label >= 0, 1)
+ *   box  = sum over positives of [w_off * (0.5 smoothL1(reg - label) + 0.5 smoothL1(reg - teacher)) over columns 0..5
+ *          + w_acls * CE(bin logits, first maximum of the label's bin columns) + w_areg * smoothL1 of the label-weighted
+ *          residual sums + w_iou * (0.5 (1 - q(box_labels)) + 0.5 (1 - q(t_box_preds))), q(b) = (rdiou(box_preds, b) *
+ *          centerness(vote_coords, b) + 1e-8)^(1/4) + w_corner * (0.3 corner(box_preds, box_labels) + 0.7
+ *          corner(box_preds, t_box_preds))] / max(#positives, 1); NaN targets of a smooth L1 count as the input.
+ *   The counts are taken over all n rows.
+ * Outputs: losses [3] = (vote, cls, box); d_vote [n, 3], d_cls [n, C], d_reg [n, 6 + 2K], d_box [n, 7] =
+ *   d(vote + cls + box)/d(input), EVERY element written: exact zeros on rows that are not vote positives (d_vote),
+ *   ignored rows (d_cls) and rows that are not positives (d_reg, d_box).  n == 0: nothing is written.
+ * ws: spx_point_head_loss_ws_bytes(n) bytes. */
+size_t spx_point_head_loss_ws_bytes(int64_t n);
+int spx_point_head_loss(const float *vote_coords, const float *cls_preds, const float *reg_preds, const float *box_preds,
+                        const float *t_cls_preds, const float *t_reg_preds, const float *t_box_preds,
+                        const int64_t *vote_cls_labels, const float *vote_reg_labels, const int64_t *cls_labels,
+                        const float *reg_labels, const float *box_labels, int64_t n, int32_t num_class,
+                        int32_t angle_bin_num, const float *params, int with_centerness, int rdiou, int corner,
+                        float *losses, float *d_vote, float *d_cls, float *d_reg, float *d_box, void *ws, size_t ws_bytes,
+                        spx_stream_t stream);
+
+/* One layer of PointSASALoss.loss_forward: scores [n, score_cols] logits, score_cols = 1 or num_class (<= 8, else
+ *   SPX_ERR_UNSUPPORTED); labels [n] int64 (> 0 the class, 0 background, -1 ignored).  The target of column c is
+ *   (label == c + 1); a one-column score meets every one of the num_class target columns.  func 0: BCE with logits, mean
+ *   over the num_class columns; func 1: sigmoid focal loss, alpha 0.25, gamma 2, summed over them.
+ * loss [1] = layer_weight * sum over rows with label >= 0 / max(#label >= 0, 1); d_scores [n, score_cols] = its
+ *   gradient, EVERY element written (exact zeros on ignored rows).  ws: spx_point_seg_loss_ws_bytes(n) bytes. */
+size_t spx_point_seg_loss_ws_bytes(int64_t n);
+int spx_point_seg_loss(const float *scores, const int64_t *labels, int64_t n, int32_t score_cols, int32_t num_class,
+                       int32_t func, float layer_weight, float *loss, float *d_scores, void *ws, size_t ws_bytes,
+                       spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,15 @@ after s_shared_fc_layer run as two HIP ops (csrc/point_head.hip, include/spx.h ย
 parameters at every call; the S_VSA_module and s_shared_fc_layer are the existing fused SA path and a GEMM.  The ops
 compute no gradient, so the head's outputs carry no autograd history.
 
-Training is still NOT ported: forward in train mode and get_loss raise NotImplementedError (the teacher forward, the
-losses, SASA's loss_forward and the statistic momentum update are missing).  What training will consume is here: the
-target assignment, assign_targets_simple / assign_targets / assign_stu_targets, each one HIP launch for the whole
-batch with no host read (point_targets.py, csrc/point_targets.hip, include/spx.h ยง16).  forward does not call them yet.
+The training FORWARD is still not ported: forward in train mode raises NotImplementedError (the teacher branch, autograd
+through the two fused ops and the statistic momentum update are missing), and get_loss, which reads what that forward
+would leave behind, raises with it.  The two ends of training around it are here:
+  - the target assignment, assign_targets_simple / assign_targets / assign_stu_targets, each one HIP launch for the
+    whole batch with no host read (point_targets.py, csrc/point_targets.hip, include/spx.h ยง16);
+  - the losses on a forward_ret_dict with the reference's keys, get_loss_torch (the torch composition) and
+    get_loss_fused (point_losses.py, csrc/point_loss.hip, include/spx.h ยง17: vote, cls and box loss with their
+    gradients from one launch group, each SASA layer from another, no host read).  Their tb_dict holds 0-d tensors
+    instead of .item() floats, as AnchorHeadTemplate's does.
 """
 import numpy as np
 import torch
@@ -21,7 +26,7 @@ from spx import ops as spx_ops
 
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...utils import box_coder_utils, loss_utils
-from . import point_targets
+from . import point_losses, point_targets
 from .point_head_template import PointHeadTemplate
 
 
@@ -222,6 +227,43 @@ class PointHeadVoteSASAStatisticDistillation(PointHeadTemplate):
                                   'forward, the vote, cls, box, corner, iou and SASA losses and the statistic momentum '
                                   'update; their targets are assign_targets_simple / assign_targets / '
                                   'assign_stu_targets)')
+
+    def _get_loss(self, ret_dict, tb_dict, fused):
+        ret_dict = self.forward_ret_dict if ret_dict is None else ret_dict
+        if ret_dict is None:
+            raise ValueError('no ret_dict given and no forward_ret_dict to read')
+        tb_dict = {} if tb_dict is None else tb_dict
+        head_loss = point_losses.head_loss_fused if fused else point_losses.head_loss_torch
+        point_loss, parts = head_loss(ret_dict, self.model_cfg, self.box_coder, self.reg_loss_func, self.cls_loss_func)
+        tb_dict.update({'point_loss_vote': parts[0], 'point_loss_cls': parts[1], 'point_loss_box': parts[2],
+                        'vote_loss_reg': parts[0],
+                        'point_pos_num': (ret_dict['s_point_cls_labels'] > 0).sum()})
+        if self.enable_sasa:
+            layer_losses = self.loss_point_sasa.loss_forward(
+                ret_dict['point_sasa_preds'], ret_dict['point_sasa_labels'], ret_dict['point_sasa'],
+                ret_dict['point_sasa_boxes'], ret_dict['point_sasa_parts'], fused=fused)
+            point_loss_sasa = None
+            for i, layer_loss in enumerate(layer_losses):
+                if layer_loss is None:
+                    continue
+                layer_loss = layer_loss.reshape(())
+                point_loss_sasa = layer_loss if point_loss_sasa is None else point_loss_sasa + layer_loss
+                tb_dict['point_loss_sasa_layer_%d' % i] = layer_loss.detach()
+            if point_loss_sasa is not None:
+                tb_dict['point_loss_sasa'] = point_loss_sasa.detach()
+                point_loss = point_loss + point_loss_sasa
+        return point_loss, tb_dict
+
+    def get_loss_torch(self, ret_dict=None, tb_dict=None):
+        """The reference's get_loss as a torch composition on ret_dict (default: forward_ret_dict) with the keys listed
+        in point_losses.py, plus point_sasa_preds / point_sasa_labels / point_sasa / point_sasa_boxes / point_sasa_parts
+        when SASA is enabled -> (point_loss, tb_dict of 0-d tensors)."""
+        return self._get_loss(ret_dict, tb_dict, fused=False)
+
+    def get_loss_fused(self, ret_dict=None, tb_dict=None):
+        """The same through the fused HIP ops: GPU tensors only, no host read (captures in a graph).  Settings the kernel
+        does not cover raise NotImplementedError."""
+        return self._get_loss(ret_dict, tb_dict, fused=True)
 
     def forward(self, batch_dict):
         """Eval forward of the student branch.

@@ -1,4 +1,5 @@
-"""Losses of the anchor head (semantics of reference pcdet/utils/loss_utils.py:9-77,140-209,310-338).
+"""Losses of the anchor head (semantics of reference pcdet/utils/loss_utils.py:9-77,140-209,310-338) and of the
+fast_cpc point head (WeightedBinaryCrossEntropyLoss, PointSASALoss: :339-362, :545-753).
 Device-agnostic: nothing is moved with .cuda() at construction."""
 import numpy as np
 import torch
@@ -62,17 +63,36 @@ class WeightedCrossEntropyLoss(nn.Module):
 
 
 class WeightedBinaryCrossEntropyLoss(nn.Module):
-    """Constructed by the fast_cpc point head (reference loss_utils.py:339).  Holds no parameters or buffers; its
-    forward belongs to the point head's training path, which is not ported yet."""
+    """Binary cross entropy with logits, mean over the classes, times the row weights (reference loss_utils.py:339-362).
+    input, target (..., #classes), weights (...) -> (...).  No parameters or buffers."""
 
     def forward(self, input, target, weights):
-        raise NotImplementedError('WeightedBinaryCrossEntropyLoss.forward: point-head training is not ported')
+        return F.binary_cross_entropy_with_logits(input, target, reduction='none').mean(dim=-1) * weights
+
+
+class _FusedPointSegLoss(torch.autograd.Function):
+    """One layer's 0-d loss with d(loss)/d(scores) from one libspx launch group (csrc/point_loss.hip); backward scales
+    the saved gradient."""
+
+    @staticmethod
+    def forward(ctx, scores, labels, num_class, func, layer_weight):
+        from spx import ops
+        loss, d_scores = ops.point_seg_loss(scores, labels, num_class, func, layer_weight)
+        ctx.save_for_backward(d_scores)
+        ctx.shape = scores.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_scores, = ctx.saved_tensors
+        return (d_scores * g).view(ctx.shape), None, None, None, None
 
 
 class PointSASALoss(nn.Module):
     """The reference's layer-wise SASA segmentation loss (loss_utils.py:545-704) up to its targets: the constructor
     (no parameters or buffers), assign_target and forward, which assigns the targets of every weighted layer, one HIP
-    launch per layer for the whole batch and no host read.  loss_forward, the loss itself, is not ported yet."""
+    launch per layer for the whole batch and no host read, and loss_forward, the loss of every layer that has scores and
+    labels: fused (forward and gradient from csrc/point_loss.hip, no host read) or as the reference's torch composition."""
 
     def __init__(self, func='BCE', layer_weights=None, extra_width=None, set_ignore_flag=False, num_class=None):
         super().__init__()
@@ -109,3 +129,30 @@ class PointSASALoss(nn.Module):
             l_boxes.append(li_boxes)
             l_parts.append(li_parts)
         return l_labels, l_boxes, l_parts
+
+    def loss_forward(self, l_scores, l_labels, l_points, l_boxes, l_parts, fused=True):
+        """l_scores: per layer (N, 1) or (N, num_class) logits or None; l_labels: per layer (N) long (> 0 the class, 0
+        background, -1 ignored) or None -> per layer the 0-d layer_weight * sum / clamp(#labels >= 0, 1), or None.
+        The target is the one-hot of the class without its background column; a one-column score meets every one of
+        the num_class target columns (with 3 classes a foreground row is one positive and two negative terms).
+        l_points, l_boxes and l_parts are not read, as in the reference.  fused needs GPU tensors."""
+        focal = isinstance(self.loss_func, SigmoidFocalClassificationLoss)
+        if fused and focal and (self.loss_func.alpha != 0.25 or self.loss_func.gamma != 2.0):
+            raise NotImplementedError('fused SASA loss: focal alpha 0.25, gamma 2 only')
+        l_loss = []
+        for i in range(len(self.layer_weights)):
+            li_scores, li_labels = l_scores[i], l_labels[i]
+            if li_scores is None or li_labels is None:
+                l_loss.append(None)
+                continue
+            if fused:
+                l_loss.append(_FusedPointSegLoss.apply(li_scores, li_labels, self.num_class, int(focal),
+                                                       float(self.layer_weights[i])))
+                continue
+            cls_weights = (li_labels >= 0).to(li_scores.dtype)
+            one_hot = li_scores.new_zeros(*li_labels.shape, self.num_class + 1)
+            one_hot.scatter_(-1, (li_labels * (li_labels > 0).long()).unsqueeze(-1), 1.0)
+            one_hot = one_hot[:, 1:]
+            li_loss = self.loss_func(li_scores.expand_as(one_hot)[None], one_hot[None], cls_weights.reshape(1, -1))
+            l_loss.append(self.layer_weights[i] * li_loss.sum() / torch.clamp(cls_weights.sum(dim=0), min=1.0))
+        return l_loss

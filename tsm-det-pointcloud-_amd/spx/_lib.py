@@ -140,6 +140,12 @@ SIGNATURES = {
     "spx_point_assign_targets": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _f32p, ctypes.c_int32,
                                         ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
+    "spx_point_head_loss_ws_bytes": (_sz, [_i64]),
+    "spx_point_head_loss": (_int, [_vp] * 12 + [_i64, ctypes.c_int32, ctypes.c_int32, _f32p, _int, _int, _int, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_point_seg_loss_ws_bytes": (_sz, [_i64]),
+    "spx_point_seg_loss": (_int, [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp,
+                                  _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

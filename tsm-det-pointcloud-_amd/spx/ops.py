@@ -1345,3 +1345,97 @@ def point_assign_targets(points, gt_boxes, mode, extra_width=None, central_radiu
                                        _ptr(out.get("center_labels")), _ptr(out.get("reg_labels")),
                                        _ptr(out.get("centerness")), _stream(points)), "spx_point_assign_targets")
     return out
+
+
+# --------------------------------------------------------------------------------------- point-head losses (§17)
+
+SEG_BCE, SEG_FOCAL = 0, 1
+
+
+def _rows_f32(name, t, rows, cols):
+    """t as a contiguous fp32 (rows, cols) device tensor, without a copy when it already is one."""
+    if t.dim() != 2 or t.shape[0] != rows or (cols is not None and t.shape[1] != cols) or not t.is_floating_point():
+        raise _lib.SpxError("%s: shape %s %s, expected float (%d, %s)" % (name, tuple(t.shape), t.dtype, rows, cols))
+    return _f32(t)
+
+
+def _labels_i64(name, t, rows):
+    if t.dim() != 1 or t.shape[0] != rows or t.dtype != torch.int64:
+        raise _lib.SpxError("%s: shape %s %s, expected int64 (%d,)" % (name, tuple(t.shape), t.dtype, rows))
+    return t.detach().contiguous()
+
+
+def point_head_loss(vote_coords, cls_preds, reg_preds, box_preds, t_cls_preds, t_reg_preds, t_box_preds, vote_cls_labels,
+                    vote_reg_labels, cls_labels, reg_labels, box_labels, loss_weights, beta=1.0 / 9.0, centerness_min=0.0,
+                    centerness_max=1.0, with_centerness=True, rdiou=True, corner=True):
+    """spx_point_head_loss: the student's vote_coords (N, 3), cls_preds (N, C), reg_preds (N, 6 + 2K), box_preds (N, 7),
+    the teacher's t_cls_preds, t_reg_preds, t_box_preds, and the targets vote_cls_labels (N) int64, vote_reg_labels
+    (N, 3), cls_labels (N) int64, reg_labels (N, 6 + 2K), box_labels (N, 7); loss_weights: the eight LOSS_WEIGHTS in the
+    order of include/spx.h §17 -> (losses fp32[3] = (vote, cls, box) weighted and normalised as get_loss does, d_vote,
+    d_cls, d_reg, d_box = d(vote + cls + box)/d(the student's four inputs), every element written).  No host read."""
+    tensors = (vote_coords, cls_preds, reg_preds, box_preds, t_cls_preds, t_reg_preds, t_box_preds, vote_cls_labels,
+               vote_reg_labels, cls_labels, reg_labels, box_labels)
+    _need_gpu(*tensors)
+    lib = _lib.load()
+    if vote_coords.dim() != 2 or cls_preds.dim() != 2 or reg_preds.dim() != 2:
+        raise _lib.SpxError("point_head_loss: vote_coords %s, cls_preds %s, reg_preds %s are not (N, 3), (N, C), "
+                            "(N, 6 + 2K)" % (tuple(vote_coords.shape), tuple(cls_preds.shape), tuple(reg_preds.shape)))
+    n, c, width = vote_coords.shape[0], cls_preds.shape[1], reg_preds.shape[1]
+    bins = (width - 6) // 2
+    if width != 6 + 2 * bins or bins < 1 or c < 1:
+        raise _lib.SpxError("point_head_loss: reg_preds has %d columns, expected 6 + 2 * angle_bin_num; %d classes"
+                            % (width, c))
+    loss_weights = [float(v) for v in loss_weights]
+    if len(loss_weights) != 8:
+        raise _lib.SpxError("point_head_loss: loss_weights takes 8 values, got %d" % len(loss_weights))
+    vote_coords = _rows_f32("vote_coords", vote_coords, n, 3)
+    cls_preds, t_cls_preds = _rows_f32("cls_preds", cls_preds, n, c), _rows_f32("t_cls_preds", t_cls_preds, n, c)
+    reg_preds, t_reg_preds = _rows_f32("reg_preds", reg_preds, n, width), _rows_f32("t_reg_preds", t_reg_preds, n, width)
+    box_preds, t_box_preds = _rows_f32("box_preds", box_preds, n, 7), _rows_f32("t_box_preds", t_box_preds, n, 7)
+    vote_reg_labels = _rows_f32("vote_reg_labels", vote_reg_labels, n, 3)
+    reg_labels, box_labels = _rows_f32("reg_labels", reg_labels, n, width), _rows_f32("box_labels", box_labels, n, 7)
+    vote_cls_labels = _labels_i64("vote_cls_labels", vote_cls_labels, n)
+    cls_labels = _labels_i64("cls_labels", cls_labels, n)
+    dev = vote_coords.device
+    losses = torch.empty((3,), dtype=torch.float32, device=dev)
+    d_vote, d_cls = torch.empty_like(vote_coords), torch.empty_like(cls_preds)
+    d_reg, d_box = torch.empty_like(reg_preds), torch.empty_like(box_preds)
+    if n == 0:
+        losses.zero_()
+        return losses, d_vote, d_cls, d_reg, d_box
+    params = f_arr(loss_weights + [float(beta), float(centerness_min), float(centerness_max)])
+    wsb = lib.spx_point_head_loss_ws_bytes(n)
+    ws = workspace(dev, wsb)
+    check(lib.spx_point_head_loss(_ptr(vote_coords), _ptr(cls_preds), _ptr(reg_preds), _ptr(box_preds), _ptr(t_cls_preds),
+                                  _ptr(t_reg_preds), _ptr(t_box_preds), _ptr(vote_cls_labels), _ptr(vote_reg_labels),
+                                  _ptr(cls_labels), _ptr(reg_labels), _ptr(box_labels), n, c, bins, params,
+                                  int(bool(with_centerness)), int(bool(rdiou)), int(bool(corner)), _ptr(losses),
+                                  _ptr(d_vote), _ptr(d_cls), _ptr(d_reg), _ptr(d_box), _ptr(ws), wsb, _stream(vote_coords)),
+          "spx_point_head_loss")
+    return losses, d_vote, d_cls, d_reg, d_box
+
+
+def point_seg_loss(scores, labels, num_class, func, layer_weight):
+    """spx_point_seg_loss (one layer of PointSASALoss.loss_forward): scores (N, 1) or (N, num_class) logits, labels (N)
+    int64 (> 0 the class, 0 background, -1 ignored), func SEG_BCE or SEG_FOCAL -> (loss fp32[1] = layer_weight * sum /
+    max(#labels >= 0, 1), d_scores like scores).  No host read."""
+    _need_gpu(scores, labels)
+    lib = _lib.load()
+    if scores.dim() != 2:
+        raise _lib.SpxError("point_seg_loss: scores %s are not (N, 1) or (N, num_class)" % (tuple(scores.shape),))
+    n, s = scores.shape
+    num_class = int(num_class)
+    if s not in (1, num_class) or int(func) not in (SEG_BCE, SEG_FOCAL):
+        raise _lib.SpxError("point_seg_loss: %d score columns for %d classes, func %s" % (s, num_class, func))
+    scores, labels = _rows_f32("scores", scores, n, s), _labels_i64("labels", labels, n)
+    dev = scores.device
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    d_scores = torch.empty_like(scores)
+    if n == 0:
+        loss.zero_()
+        return loss, d_scores
+    wsb = lib.spx_point_seg_loss_ws_bytes(n)
+    ws = workspace(dev, wsb)
+    check(lib.spx_point_seg_loss(_ptr(scores), _ptr(labels), n, s, num_class, int(func), float(layer_weight), _ptr(loss),
+                                 _ptr(d_scores), _ptr(ws), wsb, _stream(scores)), "spx_point_seg_loss")
+    return loss, d_scores
