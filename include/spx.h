@@ -301,7 +301,8 @@ int spx_densify_bwd(const float *ddense, const int32_t *idx, int64_t n, const in
  *      pcdet/ops/iou3d_nms/src/iou3d_nms_kernel.cu:236-325, src/iou3d_nms.cpp:53-190, called from
  *      pcdet/ops/iou3d_nms/iou3d_nms_utils.py:48-118 by model_nms_utils.py:6-87.
  *    boxes are device [n,7] fp32 (x,y,z,dx,dy,dz,heading).
- *    spx_boxes_iou_bev : out[n,m] = BEV IoU (overlap_only != 0: intersection AREA) of every pair.
+ *    spx_boxes_iou_bev : out[n,m] = BEV IoU (overlap_only != 0: intersection AREA) of every pair.  The IoU is at
+ *                        most 1 (csrc/box_iou.h).  n * m == 0 is a no-op and `out` may then be NULL.
  *    spx_nms_bev       : boxes must already be sorted by descending score; keep[0..*d_num_keep) receives the kept
  *                        positions in ascending order (greedy: a box is kept iff no earlier kept box has IoU > thresh).
  *                        axis_aligned != 0 uses the heading-less IoU of nms_normal_gpu.  The suppression mask and its

@@ -2,7 +2,8 @@
 
 Ordering is a stable descending sort, so equal scores keep the lower row first.  The pair IoUs come from the library's
 own IoU matrix (ops.boxes_iou_bev, entry [i, j] = iou(box i, box j)), read as [earlier, later]; the greedy loops run on
-the host.  The axis-aligned IoU has no matrix entry point: it is restated in float64 and the caller must give inputs
+the host.  That matrix is pinned to a float64 reference of its own, and the three NMS paths to one decision per pair, in
+tests/box_iou_ref.py / tests/test_gpu_box_iou.py.  The axis-aligned IoU has no matrix entry point: it is restated in float64 and the caller must give inputs
 whose IoUs keep clear of the NMS threshold (checked here), so that fp32 rounding cannot change a decision.
 Recall follows the reference's generate_recall_record with iou3d_nms_utils.boxes_iou3d_gpu."""
 import numpy as np

@@ -6,8 +6,27 @@
 // straddle tests} U {corners of one box inside the other with a 1e-2 margin}, vertices sorted by angle around their
 // centroid, shoelace area (reference pcdet/ops/iou3d_nms/src/iou3d_nms_kernel.cu:30-235, CPU twin
 // src/iou3d_cpu.cpp:30-252).  The argument order matters to the last bit: callers pass (earlier box, later box).
+//
+// Three departures, no-ops wherever the reference's arithmetic is sound (tests/box_iou_ref.py restates them):
+//   - a crossing point is moved onto the rectangle that the two segments' bounding boxes share.  Two edges on one line
+//     (boxes flush along an edge, at a heading where the cross products do not cancel exactly) can pass the straddle
+//     test by rounding alone, and the point then computed lies anywhere on that line: the reference returns an area that
+//     is off by the box's own size.  On the shared rectangle the point is a boundary point of the intersection.
+//   - where the two edges are parallel to within kEps, the reference solves the two line equations, dividing
+//     differences of coordinate products by a determinant below kEps: in fp32 that is noise as soon as the coordinates
+//     exceed the edge lengths.  Here the point is q0 + t (q1 - q0) with t = s1 / (s1 - s5) clamped to [0, 1]: on q.
+//   - the IoU is capped at 1.  Corners taken in by the margin can make the polygon larger than either box (boxes a few
+//     centimetres in size, near-duplicates), and the ratio then exceeds 1 by anything up to 1 / kEps.  No suppression
+//     decision at a threshold below 1 changes.
+//
+// FMA contraction is off from here to the end of every file that includes this header.  Left to the compiler, the cross
+// products contract differently in each kernel the pair test is inlined into: k_nms_mask and k_iou_bev have returned
+// IoUs one ulp apart for the same pair, and with them different keep lists at a threshold equal to that IoU
+// (tests/test_gpu_box_iou.py).  Every fp32 operation below now rounds once, in source order, in every caller.
 #pragma once
 #include "spx_common.h"
+
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -44,12 +63,14 @@ __device__ __forceinline__ bool seg_cross(const P2& p1, const P2& p0, const P2& 
     ans->x = (s5 * q0.x - s1 * q1.x) / (s5 - s1);
     ans->y = (s5 * q0.y - s1 * q1.y) / (s5 - s1);
   } else {
-    float a0 = p0.y - p1.y, b0 = p1.x - p0.x, c0 = p0.x * p1.y - p1.x * p0.y;
-    float a1 = q0.y - q1.y, b1 = q1.x - q0.x, c1 = q0.x * q1.y - q1.x * q0.y;
-    float D = a0 * b1 - a1 * b0;
-    ans->x = (b0 * c1 - b1 * c0) / D;
-    ans->y = (a1 * c0 - a0 * c1) / D;
+    // parallel to rounding: the point of q at the clamped parameter (fmaxf first, so that a NaN becomes 0)
+    float t = fminf(fmaxf(s1 / (s1 - s5), 0.f), 1.f);
+    ans->x = q0.x + t * (q1.x - q0.x);
+    ans->y = q0.y + t * (q1.y - q0.y);
   }
+  // onto the shared rectangle (not empty: bbox_overlap holds); fmaxf first, so that a NaN goes to the lower end
+  ans->x = fminf(fmaxf(ans->x, fmaxf(fminf(p0.x, p1.x), fminf(q0.x, q1.x))), fminf(fmaxf(p0.x, p1.x), fmaxf(q0.x, q1.x)));
+  ans->y = fminf(fmaxf(ans->y, fmaxf(fminf(p0.y, p1.y), fminf(q0.y, q1.y))), fminf(fmaxf(p0.y, p1.y), fmaxf(q0.y, q1.y)));
   return true;
 }
 
@@ -120,7 +141,7 @@ __device__ float overlap_area(const float* a, const float* b) {
 __device__ __forceinline__ float iou_bev(const float* a, const float* b) {
   float sa = a[3] * a[4], sb = b[3] * b[4];
   float so = overlap_area(a, b);
-  return so / fmaxf(sa + sb - so, kEps);
+  return fminf(so / fmaxf(sa + sb - so, kEps), 1.0f);
 }
 
 __device__ __forceinline__ float iou_normal(const float* a, const float* b) {

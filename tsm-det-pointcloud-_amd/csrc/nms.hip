@@ -92,8 +92,9 @@ __global__ __launch_bounds__(64) void k_nms_reduce(const unsigned long long* __r
 
 extern "C" int spx_boxes_iou_bev(const float* boxes_a, int64_t n, const float* boxes_b, int64_t m, int overlap_only,
                                  float* out, spx_stream_t stream) {
-  if ((!boxes_a && n > 0) || (!boxes_b && m > 0) || !out || n < 0 || m < 0) return SPX_ERR_INVALID_ARG;
-  if (n * m == 0) return SPX_OK;
+  if ((!boxes_a && n > 0) || (!boxes_b && m > 0) || n < 0 || m < 0) return SPX_ERR_INVALID_ARG;
+  if (n * m == 0) return SPX_OK;      // an empty matrix has no storage to point at
+  if (!out) return SPX_ERR_INVALID_ARG;
   if (n * m >= (int64_t(1) << 40)) return SPX_ERR_TOO_LARGE;
   hipLaunchKernelGGL(k_iou_bev, dim3((unsigned)((n * m + 255) / 256)), dim3(256), 0, spx_s(stream), boxes_a, n, boxes_b, m,
                      out, overlap_only);
