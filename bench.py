@@ -2,7 +2,8 @@
 VoxelBackBone8x hot path, KITTI-shaped synthetic frames (BASELINE.json configs[1]: ~20k points, 16k active voxels
 per frame, batch 4 per GPU), one process per GPU.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5            # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     # + roofline, per-kernel table, extras, CPU baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +15,9 @@ gradient all-reduce (RCCL over xGMI).  Rank 0 prints ONE JSON line.
 `--gpus N` without a torchrun environment: the parent starts the N ranks itself (torch.distributed.run, 127.0.0.1) BEFORE
 it touches the GPU, forwards rank 0's line and exits with the children's code; under torchrun WORLD_SIZE must equal --gpus.
 
-Besides the contract fields the line carries
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line with the contract fields and
+the workload's `config`.  Everything else the benchmark measures takes runs of its own after the timed region and is done
+only with `--full` (each leg can still be switched off there with its `--no-...` option); the line then also carries
   extras        (N = 1 only, each timed in-process after the headline) `forward` (cfg 2 full detector, eager and one
                 hipGraph), `backbone_forward` (voxelise -> VoxelBackBone8x -> densify only, eager and hipGraph, with its own
                 roofline from the per-layer algorithmic bytes / FLOPs of SURVEY.md §8(d)), `rulebook_mvoxels_s` (submanifold
@@ -68,9 +71,13 @@ def parse():
                     help="do not load the tuned MIOpen user database shipped in tsm-det-pointcloud-_amd/miopen_db (solver "
                          "choices of MIOpen's own tuner for the dense tail's convolutions; immediate mode then uses MIOpen's "
                          "system database)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward / backbone / rulebook / Waymo extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline / per-kernel table, the extras and the CPU baseline "
+                         "(a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the instrumented steps (roofline, kernels)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the forward / backbone / rulebook / Waymo extras")
     ap.add_argument("--graph", action="store_true",
                     help="single-GPU training: replay forward + backward as one hipGraph (GraphedTrainStep) instead of issuing "
                          "them kernel by kernel; measured SLOWER than eager on MI355X (298 vs 310 frames/s, DESIGN.md 6b)")
@@ -909,7 +916,7 @@ def main():
                                     if caps is not None else "exact-size sparse tensors"},
         }
     # ---- roofline: instrumented extra steps of the same workload (rank 0 prints; all ranks run them so DDP stays in step)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         kt = KernelTimer()
         kt.install()
         # The instrumented steps run the SAME execution mode as the timed ones (static capacities: no host read inside the step,
@@ -944,10 +951,10 @@ def main():
                                      % (k, v["ms_per_step"], v["launches_per_step"], v["flops"] / n_inst / 1e9,
                                         v["bytes"] / n_inst / 1e6, v["flops"] / (v["ms"] * 1e-3) / 1e12,
                                         v["bytes"] / (v["ms"] * 1e-3) / 1e9))
-    if rank == 0 and world == 1 and not args.no_extras and args.mode == "train" and args.cfg == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.mode == "train" and args.cfg == 2:
         core = model.module if hasattr(model, "module") else model
         line["extras"] = extras(core, batches, batch, device, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.cfg, args.mode)
     if rank == 0:
         print(json.dumps(line))

@@ -1,5 +1,6 @@
-"""bench.py end to end on the GPU box: the default command line's instrumented steps wrap every spx.ops entry point, so a new
-keyword argument in ops that the wrappers do not pass through breaks the round's headline run (it did once, round 3)."""
+"""bench.py end to end on the GPU: the instrumented steps of a `--full` run wrap every spx.ops entry point, so a new keyword
+argument in ops that the wrappers do not pass through breaks that run (it did once, round 3); a plain run prints the headline
+line alone."""
 import json
 import os
 import subprocess
@@ -15,9 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_with_roofline_and_kernels(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     dump = tmp_path / "outputs"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-extras", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, env=env,
-                       cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--full",
+                        "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(dump)], capture_output=True, text=True,
+                       timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-500:]
@@ -43,15 +44,21 @@ def test_bench_outputs_repeat_bit_for_bit(tmp_path):
     """Two runs of the same training benchmark compute the same last step: same seeded inputs, and every reduction of the
     step in a fixed order (spx kernels; the BEV tail's stock-conv weight gradients via model_utils/det_wgrad.py — MIOpen's
     backward-weights reduces in a run-dependent order, and AdamW's first steps amplify its last-bit differences).  Ten
-    steps, so a difference in any step reaches the dumped loss, gradients and parameters."""
+    steps, so a difference in any step reaches the dumped loss, gradients and parameters.  Both are plain runs (no --full):
+    their line carries the headline and none of the legs that take runs of their own."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     dumps = []
     for run in ("a", "b"):
         dumps.append(tmp_path / run)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "4", "--no-cpu-baseline",
-                            "--no-extras", "--no-roofline", "--dump-outputs", str(dumps[-1])], capture_output=True, text=True,
-                           timeout=600, env=env, cwd=ROOT)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "4",
+                            "--dump-outputs", str(dumps[-1])], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-500:]
+        d = json.loads(lines[0])
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["steps"] == 6 and d["warmup"] == 4
+        assert not {"roofline", "kernels", "extras", "cpu_baseline"} & set(d), sorted(d)
     names = sorted(f.name for f in dumps[0].iterdir())
     assert names == sorted(f.name for f in dumps[1].iterdir()) and len(names) > 100
     differ = [n for n in names if not np.array_equal(np.load(dumps[0] / n), np.load(dumps[1] / n))]

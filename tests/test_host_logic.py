@@ -135,6 +135,17 @@ def test_bench_launcher_refuses_what_it_cannot_run():
     assert r.returncode == 2 and "WORLD_SIZE=4" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_full_is_an_option_and_off_by_default(monkeypatch):
+    """`--full` gates every leg of bench.py that takes runs of its own; a plain command line does not ask for it."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    args = bench.parse()
+    assert args.full is True and not (args.no_roofline or args.no_extras or args.no_cpu_baseline)
+
+
 def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
     """`bench.py --dump-outputs`: float32 / float64 files only, whole when they fit, otherwise a seeded sample of the large
     arrays that keeps the total within the budget and is the same from run to run.  Host-only: no GPU touched."""
