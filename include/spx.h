@@ -773,6 +773,80 @@ int spx_point_seg_loss(const float *scores, const int64_t *labels, int64_t n, in
                        int32_t func, float layer_weight, float *loss, float *d_scores, void *ws, size_t ws_bytes,
                        spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 18. Stacked (ragged-batch) point ops (PV-RCNN-style set abstraction over (N1 + N2 + ..., C) tensors;
+ *     csrc/pointnet2_stack.hip)
+ *    replaces: the rest of the pointnet2_stack extension (§10 holds its voxel query), reference
+ *      pcdet/ops/pointnet2/pointnet2_stack/src/ (ball_query, group_points, sampling, interpolate _gpu.cu), reached from
+ *      pointnet2_utils.py, pointnet2_modules.py and voxel_pool_modules.py.
+ *    All tensors fp32 / int32, contiguous, row-major; b frames, 1 <= b <= 256 (more: SPX_ERR_UNSUPPORTED).  Every
+ *    *_batch_cnt is an int32 DEVICE array of b counts that no call reads on the host: the row counts (n_rows, m_rows)
+ *    are the tensors' shapes, frame starts are exclusive prefix sums taken on the device (negative counts count as 0, sums
+ *    are clamped to the row count).  Rows past the sum of the counts are DEAD (static capacity for graph capture): a dead
+ *    query row gets the fill stated below, a dead output row is 0, a dead source row is never read and gets a zero
+ *    gradient.  No kernel reads or writes outside the given row counts, whatever the indices or counts hold: a bad index
+ *    reads as 0 in a forward pass and is dropped in a backward pass (the §11 convention).  Distances are
+ *    ((dx*dx)+(dy*dy))+(dz*dz), dx = a - b, rounded after every operation (no FMA contraction).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* replaces: ball_query_wrapper (ball_query_gpu.cu:16-66) and the empty-ball fix-up of BallQuery.forward
+ *   (pointnet2_utils.py:8-38).  xyz [n_rows, 3]; new_xyz [m_rows, 3] centres.  The hits of a query are the frame-local
+ *   k (ascending) of its frame's points with d2 < radius*radius (the product in fp32); the first nsample are kept and
+ *   the unfilled slots hold the FIRST hit.  idx [m_rows, nsample]; empty [m_rows] bytes: 1 for a ball without a hit,
+ *   whose idx is all 0.  Dead rows: idx 0, empty 1.  Every slot is written.  One thread per query; a workgroup's
+ *   queries lie in one frame (device-side map of workgroups to (frame, tile) pairs) and share its points through LDS. */
+int spx_stack_ball_query(const float *xyz, const int32_t *xyz_batch_cnt, const float *new_xyz,
+                         const int32_t *new_xyz_batch_cnt, int32_t b, int64_t n_rows, int64_t m_rows, float radius,
+                         int32_t nsample, int32_t *idx, uint8_t *empty, spx_stream_t stream);
+
+/* replaces: group_points_wrapper (group_points_gpu.cu, pointnet2_utils.py:48-82).  features [n_rows, c]; idx
+ *   [m_rows, nsample] frame-local rows; out [m_rows, c, nsample] = features[start(frame of m) + idx[m, s], c]; an index
+ *   outside its frame reads as 0; dead rows are 0. */
+int spx_stack_group_points(const float *features, const int32_t *features_batch_cnt, const int32_t *idx,
+                           const int32_t *idx_batch_cnt, int32_t b, int64_t n_rows, int64_t m_rows, int32_t c,
+                           int32_t nsample, float *out, spx_stream_t stream);
+
+/* replaces: group_points_grad_wrapper (atomicAdd there).  grad_out [m_rows, c, nsample] -> grad_features [n_rows, c],
+ *   every element written, DETERMINISTIC and without float atomics: the entries are stable-sorted by global target row
+ *   (radix sort in ws), each target's run is added in ascending entry order in pieces of at most 128 sorted positions,
+ *   and the pieces of a run that crosses such a border are added in ascending order afterwards. */
+size_t spx_stack_group_points_bwd_ws_bytes(int64_t n_rows, int64_t m_rows, int32_t c, int32_t nsample);
+int spx_stack_group_points_bwd(const float *grad_out, const int32_t *features_batch_cnt, const int32_t *idx,
+                               const int32_t *idx_batch_cnt, int32_t b, int64_t n_rows, int64_t m_rows, int32_t c,
+                               int32_t nsample, float *grad_features, void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* replaces: three_nn_wrapper (interpolate_gpu.cu, pointnet2_utils.py:224-257).  unknown [n_rows, 3], known [m_rows, 3];
+ *   dist2 [n_rows, 3] squared distances and idx [n_rows, 3] GLOBAL known rows (frame start + k) of the three nearest
+ *   known points of the same frame (strict-< insertion in ascending k).  Unfilled slots (a frame with fewer than 3 known
+ *   points) hold inf and the frame start; dead rows hold inf and 0. */
+int spx_stack_three_nn(const float *unknown, const int32_t *unknown_batch_cnt, const float *known,
+                       const int32_t *known_batch_cnt, int32_t b, int64_t n_rows, int64_t m_rows, float *dist2,
+                       int32_t *idx, spx_stream_t stream);
+
+/* replaces: three_interpolate_wrapper / three_interpolate_grad_wrapper (interpolate_gpu.cu, pointnet2_utils.py:260-299).
+ *   features [m_rows, c]; idx (global rows), weight [n_rows, 3]; out [n_rows, c] = ((w0*f0) + (w1*f1)) + (w2*f2).
+ *   batch_cnt [b]: the counts of the n side, or NULL (b ignored): every row is live.  Dead rows are 0 (their weights,
+ *   0 / 0 from the infinite distances, are not read).  The backward writes all of grad_features [m_rows, c],
+ *   deterministically as spx_stack_group_points_bwd does, the products grad_out * weight being the contributions. */
+int spx_stack_three_interpolate(const float *features, const int32_t *idx, const float *weight, const int32_t *batch_cnt,
+                                int32_t b, int64_t m_rows, int64_t n_rows, int32_t c, float *out, spx_stream_t stream);
+size_t spx_stack_three_interpolate_bwd_ws_bytes(int64_t m_rows, int64_t n_rows, int32_t c);
+int spx_stack_three_interpolate_bwd(const float *grad_out, const int32_t *idx, const float *weight,
+                                    const int32_t *batch_cnt, int32_t b, int64_t m_rows, int64_t n_rows, int32_t c,
+                                    float *grad_features, void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* replaces: stack_farthest_point_sampling_wrapper (sampling_gpu.cu:187-349, pointnet2_utils.py:187-221).  xyz
+ *   [n_rows, 3]; npoint [b] DEVICE int32 picks per frame; idx [out_rows] GLOBAL rows, frame f writing npoint[f] picks at
+ *   the prefix sum of npoint (clamped to out_rows; the caller sizes out_rows to the sum).  The first pick of a frame is
+ *   its first row; later picks as spx_furthest_point_sample, unweighted, with the tie priority of the reference's fixed
+ *   1024 threads: (bitrev10(k mod 1024), k div 1024), whatever the frame's size.  npoint above the frame's size is
+ *   legal; a frame without points picks its frame start every time and reads nothing.  Frames of up to 16384 points run
+ *   from registers; ws (n_rows floats) is needed only when n_rows is larger. */
+size_t spx_stack_furthest_point_sample_ws_bytes(int64_t n_rows);
+int spx_stack_furthest_point_sample(const float *xyz, const int32_t *xyz_batch_cnt, const int32_t *npoint, int32_t b,
+                                    int64_t n_rows, int64_t out_rows, int32_t *idx, void *ws, size_t ws_bytes,
+                                    spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

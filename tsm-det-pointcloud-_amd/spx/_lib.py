@@ -146,6 +146,20 @@ SIGNATURES = {
     "spx_point_seg_loss_ws_bytes": (_sz, [_i64]),
     "spx_point_seg_loss": (_int, [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp,
                                   _vp, _vp, _sz, _vp]),
+    "spx_stack_ball_query": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_float, ctypes.c_int32, _vp,
+                                    _vp, _vp]),
+    "spx_stack_group_points": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp,
+                                      _vp]),
+    "spx_stack_group_points_bwd_ws_bytes": (_sz, [_i64, _i64, ctypes.c_int32, ctypes.c_int32]),
+    "spx_stack_group_points_bwd": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_int32, ctypes.c_int32,
+                                          _vp, _vp, _sz, _vp]),
+    "spx_stack_three_nn": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp, _vp]),
+    "spx_stack_three_interpolate": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp]),
+    "spx_stack_three_interpolate_bwd_ws_bytes": (_sz, [_i64, _i64, ctypes.c_int32]),
+    "spx_stack_three_interpolate_bwd": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp,
+                                               _sz, _vp]),
+    "spx_stack_furthest_point_sample_ws_bytes": (_sz, [_i64]),
+    "spx_stack_furthest_point_sample": (_int, [_vp, _vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1439,3 +1439,137 @@ def point_seg_loss(scores, labels, num_class, func, layer_weight):
     check(lib.spx_point_seg_loss(_ptr(scores), _ptr(labels), n, s, num_class, int(func), float(layer_weight), _ptr(loss),
                                  _ptr(d_scores), _ptr(ws), wsb, _stream(scores)), "spx_point_seg_loss")
     return loss, d_scores
+
+
+# ------------------------------------------------------------------------- stacked (ragged-batch) point ops (§18)
+
+def _cnt(name, cnt, dev):
+    """A *_batch_cnt as the kernels read it: int32, contiguous, on the device.  Never read here."""
+    if cnt.dim() != 1 or cnt.shape[0] < 1:
+        raise _lib.SpxError("%s: expected (batch_size,) counts, got %s" % (name, tuple(cnt.shape)))
+    if cnt.device != dev:
+        raise _lib.SpxError("%s lives on %s, the points on %s" % (name, cnt.device, dev))
+    return _i32(cnt)
+
+
+def stack_ball_query(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, radius, nsample):
+    """spx_stack_ball_query: xyz (N, 3), new_xyz (M, 3), counts (B,) int32 on the device -> idx (M, nsample) int32 of
+    frame-local rows (unfilled slots = the first hit) and empty (M,) bool.  Rows past the counts' sums are dead: idx 0,
+    empty True.  No host read."""
+    _need_gpu(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+    lib = _lib.load()
+    xyz, new_xyz = _f32(xyz), _f32(new_xyz)
+    dev = xyz.device
+    nc, mc = _cnt("xyz_batch_cnt", xyz_batch_cnt, dev), _cnt("new_xyz_batch_cnt", new_xyz_batch_cnt, dev)
+    n, m = xyz.shape[0], new_xyz.shape[0]
+    idx = torch.empty((m, int(nsample)), dtype=torch.int32, device=dev)
+    empty = torch.empty((m,), dtype=torch.bool, device=dev)
+    if m:
+        check(lib.spx_stack_ball_query(_ptr(xyz), _ptr(nc), _ptr(new_xyz), _ptr(mc), nc.shape[0], n, m, float(radius),
+                                       int(nsample), _ptr(idx), _ptr(empty), _stream(xyz)), "spx_stack_ball_query")
+    return idx, empty
+
+
+def stack_group_points(features, features_batch_cnt, idx, idx_batch_cnt):
+    """spx_stack_group_points: features (N, C), idx (M, S) frame-local -> (M, C, S); dead rows and bad indices read 0."""
+    _need_gpu(features, features_batch_cnt, idx, idx_batch_cnt)
+    lib = _lib.load()
+    features, idx = _f32(features), _i32(idx)
+    dev = features.device
+    nc, mc = _cnt("features_batch_cnt", features_batch_cnt, dev), _cnt("idx_batch_cnt", idx_batch_cnt, dev)
+    (n, c), (m, s) = features.shape, idx.shape
+    out = torch.empty((m, c, s), dtype=torch.float32, device=dev)
+    if out.numel():
+        check(lib.spx_stack_group_points(_ptr(features), _ptr(nc), _ptr(idx), _ptr(mc), nc.shape[0], n, m, c, s, _ptr(out),
+                                         _stream(features)), "spx_stack_group_points")
+    return out
+
+
+def stack_group_points_bwd(grad_out, features_batch_cnt, idx, idx_batch_cnt, n):
+    """spx_stack_group_points_bwd: grad_out (M, C, S) -> grad_features (n, C), summed in a fixed order."""
+    _need_gpu(grad_out, features_batch_cnt, idx, idx_batch_cnt)
+    lib = _lib.load()
+    grad_out, idx = _f32(grad_out), _i32(idx)
+    dev = grad_out.device
+    nc, mc = _cnt("features_batch_cnt", features_batch_cnt, dev), _cnt("idx_batch_cnt", idx_batch_cnt, dev)
+    m, c, s = grad_out.shape
+    grad = torch.empty((int(n), c), dtype=torch.float32, device=dev)
+    if grad.numel():
+        wsb = lib.spx_stack_group_points_bwd_ws_bytes(int(n), m, c, s)
+        ws = workspace(dev, wsb)
+        check(lib.spx_stack_group_points_bwd(_ptr(grad_out), _ptr(nc), _ptr(idx), _ptr(mc), nc.shape[0], int(n), m, c, s,
+                                             _ptr(grad), _ptr(ws), wsb, _stream(grad_out)), "spx_stack_group_points_bwd")
+    return grad
+
+
+def stack_three_nn(unknown, unknown_batch_cnt, known, known_batch_cnt):
+    """spx_stack_three_nn: unknown (N, 3), known (M, 3) -> dist2 (N, 3) squared, idx (N, 3) int32 global known rows."""
+    _need_gpu(unknown, unknown_batch_cnt, known, known_batch_cnt)
+    lib = _lib.load()
+    unknown, known = _f32(unknown), _f32(known)
+    dev = unknown.device
+    nc, mc = _cnt("unknown_batch_cnt", unknown_batch_cnt, dev), _cnt("known_batch_cnt", known_batch_cnt, dev)
+    if nc.shape[0] != mc.shape[0]:
+        raise _lib.SpxError("stack_three_nn: %d and %d frames" % (nc.shape[0], mc.shape[0]))
+    n, m = unknown.shape[0], known.shape[0]
+    dist2 = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    if n:
+        check(lib.spx_stack_three_nn(_ptr(unknown), _ptr(nc), _ptr(known), _ptr(mc), nc.shape[0], n, m, _ptr(dist2),
+                                     _ptr(idx), _stream(unknown)), "spx_stack_three_nn")
+    return dist2, idx
+
+
+def stack_three_interpolate(features, idx, weight, batch_cnt=None):
+    """spx_stack_three_interpolate: features (M, C), idx / weight (N, 3) -> (N, C).  batch_cnt: the counts of the N side;
+    rows past their sum are written as 0 (None: every row is live)."""
+    _need_gpu(features, idx, weight, batch_cnt)
+    lib = _lib.load()
+    features, idx, weight = _f32(features), _i32(idx), _f32(weight)
+    dev = features.device
+    cnt = None if batch_cnt is None else _cnt("batch_cnt", batch_cnt, dev)
+    (m, c), n = features.shape, idx.shape[0]
+    out = torch.empty((n, c), dtype=torch.float32, device=dev)
+    if out.numel():
+        check(lib.spx_stack_three_interpolate(_ptr(features), _ptr(idx), _ptr(weight), _ptr(cnt),
+                                              0 if cnt is None else cnt.shape[0], m, n, c, _ptr(out), _stream(features)),
+              "spx_stack_three_interpolate")
+    return out
+
+
+def stack_three_interpolate_bwd(grad_out, idx, weight, m, batch_cnt=None):
+    """spx_stack_three_interpolate_bwd: grad_out (N, C) -> grad_features (m, C), summed in a fixed order."""
+    _need_gpu(grad_out, idx, weight, batch_cnt)
+    lib = _lib.load()
+    grad_out, idx, weight = _f32(grad_out), _i32(idx), _f32(weight)
+    dev = grad_out.device
+    cnt = None if batch_cnt is None else _cnt("batch_cnt", batch_cnt, dev)
+    n, c = grad_out.shape
+    grad = torch.empty((int(m), c), dtype=torch.float32, device=dev)
+    if grad.numel():
+        wsb = lib.spx_stack_three_interpolate_bwd_ws_bytes(int(m), n, c)
+        ws = workspace(dev, wsb)
+        check(lib.spx_stack_three_interpolate_bwd(_ptr(grad_out), _ptr(idx), _ptr(weight), _ptr(cnt),
+                                                  0 if cnt is None else cnt.shape[0], int(m), n, c, _ptr(grad), _ptr(ws),
+                                                  wsb, _stream(grad_out)), "spx_stack_three_interpolate_bwd")
+    return grad
+
+
+def stack_furthest_point_sample(xyz, xyz_batch_cnt, npoint, total):
+    """spx_stack_furthest_point_sample: xyz (N, 3), counts (B,), npoint (B,) int32 on the device, total = the sum of
+    npoint as the caller knows it on the host -> idx (total,) int32 global rows.  No host read."""
+    _need_gpu(xyz, xyz_batch_cnt, npoint)
+    lib = _lib.load()
+    xyz = _f32(xyz)
+    dev = xyz.device
+    nc, npt = _cnt("xyz_batch_cnt", xyz_batch_cnt, dev), _cnt("npoint", npoint, dev)
+    if nc.shape[0] != npt.shape[0]:
+        raise _lib.SpxError("stack_furthest_point_sample: %d counts, %d npoint" % (nc.shape[0], npt.shape[0]))
+    n = xyz.shape[0]
+    idx = torch.empty((int(total),), dtype=torch.int32, device=dev)
+    if idx.numel():
+        wsb = lib.spx_stack_furthest_point_sample_ws_bytes(n)
+        ws = workspace(dev, wsb) if wsb else None
+        check(lib.spx_stack_furthest_point_sample(_ptr(xyz), _ptr(nc), _ptr(npt), nc.shape[0], n, int(total), _ptr(idx),
+                                                  _ptr(ws), wsb, _stream(xyz)), "spx_stack_furthest_point_sample")
+    return idx
