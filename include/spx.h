@@ -49,6 +49,8 @@ extern "C" {
 #define SPX_ERR_RING_STALL (-8)   /* DEVICE-side: a wave of spx_conv_gemm_ring gave up a (bounded) wait on the weight ring:
                                      the launch's output is incomplete; via d_status.  Never seen; the exit exists so that a
                                      protocol fault ends as an error code and not as a hung GPU                            */
+#define SPX_ERR_OUT_OF_GRID (-9)  /* DEVICE-side: spx_voxel_table_build met a live row whose (batch, z, y, x) lies outside the
+                                     table; the row was skipped; via d_status                                               */
 
 /* flags of the entry points that keep a hash table in their workspace (spx_voxelize, spx_subm_rulebook) */
 #define SPX_WS_PRECLEARED 1 /* the caller has already initialised the workspace (hash keys = 0xFF bytes, values / point
@@ -846,6 +848,35 @@ size_t spx_stack_furthest_point_sample_ws_bytes(int64_t n_rows);
 int spx_stack_furthest_point_sample(const float *xyz, const int32_t *xyz_batch_cnt, const int32_t *npoint, int32_t b,
                                     int64_t n_rows, int64_t out_rows, int32_t *idx, void *ws, size_t ws_bytes,
                                     spx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 19. Voxel rows at static capacity (csrc/voxel_rows.hip)
+ *    replaces: generate_voxel2pinds (reference pcdet/utils/common_utils.py:257-265) for a sparse tensor whose live row
+ *      count is on the device, and the aggregation chain of the voxel-point SA modules' sparse update
+ *      (_unet_update, reference pointnet2_modules.py: get_voxel_indices -> get_centroid_per_voxel ->
+ *      get_nonempty_voxel_feature_indices -> masked assignment; two host reads there).
+ *    No host read, no atomics on data, bitwise reproducible.  Arguments are checked on the host before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* indices [cap, 4] (b, z, y, x); d_n: live rows (NULL = all cap rows); table [batch, Z, Y, X] int32, shape3 = (Z, Y, X):
+ *   -1 everywhere, then table[cell of row r] = r for every LIVE row r.  Rows at or beyond the live count are never read.
+ *   A live row outside the table is skipped and d_status (nullable, see spx_read_status) receives SPX_ERR_OUT_OF_GRID.
+ *   Two launches (fill, scatter).  cap >= 2^31 or batch * Z * Y * X >= 2^40: SPX_ERR_TOO_LARGE. */
+int spx_voxel_table_build(const int32_t *indices, int64_t cap, const int64_t *d_n, int32_t batch, const int32_t *shape3,
+                          int32_t *table, int32_t *d_status, spx_stream_t stream);
+
+/* new_xyz [batch, m, 3]; feats [batch, c, m] (channels first, read in place); table / shape3 as above; range_lo3,
+ *   voxel_size3: HOST float[3] (x, y, z).  A point's cell is trunc((p - lo) / vs) per axis, in fp32 with a correctly
+ *   rounded division; a point outside the grid is dropped.  For every distinct cell among a frame's m points the mean
+ *   of each feature column over the cell's points — the sum from 0 in ascending point order, times 1 / count, the
+ *   rounded operations of spx_dynamic_voxelize — goes to out[table[cell]] when that entry is a live row.  out [cap, c]:
+ *   every other row below the live count (d_n_rows, NULL = cap) is 0; rows at or beyond it are not written.
+ *   Two launches.  m <= 4096 (a frame's cell keys sit in LDS) and Z * Y * X < 2^31, else SPX_ERR_TOO_LARGE.
+ *   ws: spx_voxel_rows_mean_ws_bytes bytes. */
+size_t spx_voxel_rows_mean_ws_bytes(int32_t batch, int64_t m);
+int spx_voxel_rows_mean(const float *new_xyz, const float *feats, int32_t batch, int32_t c, int64_t m,
+                        const int32_t *table, const int32_t *shape3, const float *range_lo3, const float *voxel_size3,
+                        const int64_t *d_n_rows, int64_t cap, float *out, void *ws, size_t ws_bytes, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,14 @@ per-frame, per-class code (POST_PROCESSING.FUSED False) against the fused path (
 per batch) and against post_processing_static (no host read), at KITTI 4 x 512 and 16 x 512 and Waymo 4 x 3072 with each
 dataset's fast_cpc thresholds and NMS settings.  The inputs are the boxes the fused head tail decodes from random
 features at random vote positions; the logits are replaced by a permuted linspace(-3, 4), because a randomly initialised
-head scores every point near sigmoid(-4.6) and nothing would pass a KITTI threshold."""
+head scores every point near sigmoid(-4.6) and nothing would pass a KITTI threshold.
+
+Graphed inference (--graph-only), written to profiles/point3dssd_graph_bench.log: Point3DSSD at batch 4 and 16, 20 000
+points per frame.  The eager forward net(batch), the eager STATIC path (static_caps, no host read, not captured) and the
+replay of pcdet_amd.models.inference.GraphedPointDetector alternate in one process after warm-up, --windows windows of
+--iters calls each; the table gives the median window and the spread (min .. max).  Below it, the per-stage timeline of
+the eager static path from device events (the stage markers of pointnet2_modules._stage_hook), mean of --iters runs:
+device time between consecutive markers, which on an eager run includes the gaps the host leaves."""
 import argparse
 import os
 import sys
@@ -120,9 +127,149 @@ def post_process_rows(it, log_name="post_process_bench.log"):
         f.write(text)
 
 
+def _window(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+def stage_timeline(net, pts, b, iters):
+    """[(stage, mean ms)] of the eager static path, in execution order."""
+    from pcdet_amd.models.dense_heads.point_head_vote_sasa_statistic_distillation import _mlp_params
+    from pcdet_amd.ops.pointnet2.pointnet2_batch import pointnet2_modules as pm
+    from spx import ops
+    bb, head = net.backbone_3d, net.point_head
+    marks, prefix, seen = [], [""], {}
+
+    def hook(name):
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        if name in ("voxel_query", "ball_query"):
+            k = seen[prefix[0] + name] = seen.get(prefix[0] + name, 0) + 1
+            name = "%s %d" % (name, k)
+        marks.append((prefix[0] + name, ev))
+        if prefix[0] == "layer0 " and name == "centroid_aggregation":
+            prefix[0] = "layer1 "           # layer 0 ends with its aggregation; the student layer's markers follow
+
+    def run():
+        seen.clear()
+        prefix[0] = ""
+        hook("start")
+        bd = {"batch_size": b, "points": pts, "static_caps": {}}
+        prefix[0] = "layer0 "
+        bd = bb(bd)
+        hook("batch_dict")
+        prefix[0] = "head "
+        coords = bd["s_point_coords"][:, 1:4].view(b, -1, 3).contiguous()
+        f = bd["s_point_features"].reshape(b, coords.size(1), -1).permute(0, 2, 1).contiguous()
+        lo, hi = head.model_cfg.SAMPLE_RANGE
+        v = ops.point_vote(f, coords, lo, hi, _mlp_params(head.s_vote_layers), head.s_vote_cfg.MAX_TRANSLATION_RANGE)
+        hook("vote")
+        _, x, _, _, _, _, _, _ = head.S_VSA_module(
+            xyz=coords, new_xyz=v, features=bd["s_last_features"], sp_tensor=bd["s_last_sp_tensor"],
+            centroids=bd["s_last_centroids"], centroid_voxel_idxs=bd["s_last_centroid_voxel_idxs"])
+        x = head.s_shared_fc_layer(x)
+        hook("shared_fc")
+        c, r, bx = ops.point_head_predict(x, head.object_statistic_features, v.view(-1, 3),
+                                          [_mlp_params(m) for m in head.s_cls_block], _mlp_params(head.s_reg_layers),
+                                          head.box_coder.angle_bin_num)
+        torch.sigmoid(c)
+        hook("tail")
+        bidx = bd["s_point_coords"][:, 0].view(b, -1)[:, lo:hi].reshape(-1)
+        net.post_processing_static({"batch_size": b, "batch_index": bidx, "batch_cls_preds": c, "batch_box_preds": bx,
+                                    "cls_preds_normalized": False})
+        hook("post_processing_static")
+
+    pm._stage_hook = hook
+    try:
+        with torch.no_grad():
+            run()
+            torch.cuda.synchronize()
+            total, order = {}, []
+            for _ in range(iters):
+                del marks[:]
+                run()
+                torch.cuda.synchronize()
+                for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+                    if name not in total:
+                        total[name] = 0.0
+                        order.append(name)
+                    total[name] += e0.elapsed_time(e1)
+    finally:
+        pm._stage_hook = None
+    return [(name, total[name] / iters) for name in order]
+
+
+def graph_rows(iters, windows, log_name="point3dssd_graph_bench.log"):
+    """Eager / eager static / graph replay of Point3DSSD and the stage timeline (see the module docstring)."""
+    import statistics
+
+    import point_head_configs as phc
+    from pcdet_amd.models.detectors import build_detector
+    from pcdet_amd.models.inference import GraphedPointDetector
+    from spx import _lib
+    dev = torch.device("cuda:0")
+    lines = ["device: %s" % torch.cuda.get_device_name(0), "library: %s" % os.path.relpath(_lib.LIB_PATH, ROOT),
+             "Point3DSSD eval (fast_cpc KITTI config, random init), 20 000 points per frame; ms per batch, median of %d "
+             "windows of %d calls (min .. max)" % (windows, iters), "",
+             "%-8s %26s %26s %26s %9s" % ("batch", "eager net(batch)", "eager static (no graph)", "graph replay",
+                                          "eager/rep")]
+    timelines = []
+    for b in (4, 16):
+        torch.manual_seed(0)
+        net = build_detector(phc.model_cfg(), 3, phc.dataset()).to(dev).eval()
+        pts = frames(b, 20000)
+        runner = GraphedPointDetector(net, b, 20000, example=pts)
+
+        def eager():
+            with torch.no_grad():
+                net({"batch_size": b, "points": pts})
+
+        def static():
+            runner._forward()
+
+        def replay():
+            runner(pts)
+
+        for fn in (eager, static, replay):
+            fn()
+        torch.cuda.synchronize()
+        t = {"eager": [], "static": [], "replay": []}
+        for _ in range(windows):
+            t["eager"].append(_window(eager, iters))
+            t["static"].append(_window(static, iters))
+            t["replay"].append(_window(replay, iters))
+        runner.pred_dicts()                 # raises when a flag says that the batch broke the static contract
+        cell = {k: "%8.2f (%6.2f .. %6.2f)" % (statistics.median(v), min(v), max(v)) for k, v in t.items()}
+        lines.append("%-8d %26s %26s %26s %8.2fx" % (b, cell["eager"], cell["static"], cell["replay"],
+                                                     statistics.median(t["eager"]) / statistics.median(t["replay"])))
+        timelines.append((b, int(runner.out["voxel_num_valid"]), stage_timeline(net, pts, b, iters)))
+        del runner
+    for b, nvox, tl in timelines:
+        lines += ["", "stage timeline of the eager static path, batch %d (%d live voxels of %d rows), ms between markers"
+                  % (b, nvox, b * 4096)]
+        lines += ["  %-44s %9.3f" % (name, ms) for name, ms in tl]
+        lines.append("  %-44s %9.3f" % ("sum", sum(ms for _, ms in tl)))
+    lines += ["", "eager/rep = median eager time / median replay time, as measured; no ratio was fixed in advance.",
+              "Random init: no box passes the KITTI score thresholds, so post-processing has no NMS work in any column.",
+              "The timeline's stages run eagerly, so each figure includes the launch gaps of its stage; the replay has "
+              "none."]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", log_name), "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--graph-only", action="store_true", help="only the graphed-inference table and stage timeline")
+    ap.add_argument("--windows", type=int, default=5, help="timing windows per variant for --graph-only")
     ap.add_argument("--post-only", action="store_true", help="only the post-processing table")
     ap.add_argument("--post-log", default="post_process_bench.log",
                     help="file name under profiles/ for the post-processing table (an A/B against a dev build of the "
@@ -132,6 +279,9 @@ def main():
     ge.build(verbose=False)
     if args.post_only:
         post_process_rows(args.iters, args.post_log)
+        return
+    if args.graph_only:
+        graph_rows(args.iters, args.windows)
         return
     import point_head_configs as phc
     import point_head_ref as ref

@@ -4,6 +4,16 @@ pcdet/models/backbones_3d/pointnet2_backbone.py:619-923).
 A teacher stack of VoxelPointnetSAModuleFSMSGDistillation layers (SA_CONFIG) runs under no_grad; a student layer
 (S_SA_CONFIG, its layers from 1 on) runs with grad on the teacher's layer-0 output.  Same constructor, submodules and
 batch_dict keys as the reference.
+
+Static mode (batch_dict['static_caps'] is not None, the key of the SECOND path; eval and no_grad only): the forward
+reads nothing back from the device, so it can be captured in a graph.  Every frame must hold points.shape[0] /
+batch_size points.  What the backbone exposes per voxel (s_last_sp_tensor, s_last_centroids,
+s_last_centroid_voxel_idxs, s_last_scores, s_statistic_feature, point_coords_list[0], point_scores_list) then has
+B * NPOINT_LIST[0] rows of which only the first batch_dict['voxel_num_valid'] (device int64[1]) are live; the dead rows
+hold whatever the buffers held.  batch_dict['static_flags'] holds device booleans, in the manner of
+post_processing_static's layout_ok: 'layout_ok' (the frame index column is 0..B-1, each repeated equally often, in
+order) and 'in_range' (every sampled point fell into a voxel of the grid).  Where one of them is False the results of
+the batch are meaningless; nothing is raised, the caller reads the flags when convenient.
 """
 import torch
 import torch.nn as nn
@@ -125,10 +135,10 @@ class VoxelPointNet2FSMSGDistillation(nn.Module):
         return batch_idx, xyz, features
 
     @staticmethod
-    def _run(module, l, i):
+    def _run(module, l, i, static=False):
         return module(l['xyz'][i], l['features'][i], scores=l['scores'][i], part_scores=l['part_scores'][i],
                       sp_tensor=l['sp_tensor'][i], centroids=l['centroids'][i],
-                      centroid_voxel_idxs=l['centroid_voxel_idxs'][i], unique_idxs=l['unique_idxs'][i])
+                      centroid_voxel_idxs=l['centroid_voxel_idxs'][i], unique_idxs=l['unique_idxs'][i], static=static)
 
     def forward(self, batch_dict):
         """
@@ -143,8 +153,19 @@ class VoxelPointNet2FSMSGDistillation(nn.Module):
         batch_size = batch_dict['batch_size']
         points = batch_dict['points']
         batch_idx, xyz, features = self.break_up_pc(points)
-        xyz_batch_cnt = torch.bincount(batch_idx.long(), minlength=batch_size)[:batch_size]
-        assert xyz_batch_cnt.min() == xyz_batch_cnt.max()
+        static = batch_dict.get('static_caps', None) is not None
+        if static:
+            if self.training or torch.is_grad_enabled():
+                raise RuntimeError('VoxelPointNet2FSMSGDistillation: static_caps (the static-capacity path) is inference '
+                                   'only: it needs model.eval() and torch.no_grad()')
+            if batch_size < 1 or points.shape[0] == 0 or points.shape[0] % batch_size:
+                raise ValueError('VoxelPointNet2FSMSGDistillation: static mode needs %d equal, non-empty frames, got %d '
+                                 'points' % (batch_size, points.shape[0]))
+            frame = torch.arange(batch_size, device=points.device, dtype=batch_idx.dtype).view(-1, 1)
+            layout_ok = (batch_idx.view(batch_size, -1) == frame).all()
+        else:
+            xyz_batch_cnt = torch.bincount(batch_idx.long(), minlength=batch_size)[:batch_size]
+            assert xyz_batch_cnt.min() == xyz_batch_cnt.max()
         xyz = xyz.view(batch_size, -1, 3).contiguous()
         features = features.view(batch_size, -1, features.shape[-1]) if features is not None else None
         features = features.permute(0, 2, 1).contiguous() if features is not None else None
@@ -158,7 +179,7 @@ class VoxelPointNet2FSMSGDistillation(nn.Module):
         with torch.no_grad():
             aggregation_num = len(self.SA_modules) if self.training else len(self.SA_modules) - 1
             for i in range(aggregation_num):
-                for n, v in zip(names, self._run(self.SA_modules[i], l, i)):
+                for n, v in zip(names, self._run(self.SA_modules[i], l, i, static=static)):
                     l[n].append(v)
 
         # student, on the teacher's layer-0 output
@@ -205,4 +226,7 @@ class VoxelPointNet2FSMSGDistillation(nn.Module):
             batch_idx[:, :l['xyz'][-1].size(1)].reshape(-1, 1).float(), l['xyz'][-1].view(-1, 3)), dim=1)
         batch_dict['s_point_scores'] = l['scores'][-1]
         batch_dict['s_statistic_feature'] = l['sp_tensor'][-1].features
+        if static:
+            batch_dict['voxel_num_valid'] = l['sp_tensor'][-1].n_valid
+            batch_dict['static_flags'] = {'layout_ok': layout_ok, 'in_range': (l['unique_idxs'][1] >= 0).all()}
         return batch_dict

@@ -119,6 +119,103 @@ class GraphedDetector(object):
         return self.model.post_processing(dict(self.out))
 
 
+class GraphedPointDetector(object):
+    """Eval forward of a point detector (Point3DSSD: VoxelPointNet2FSMSGDistillation backbone, vote head) with its
+    post-processing as ONE hipGraph replay.
+
+    The backbone's static mode (batch_dict['static_caps'], pointnet2_backbone.py) keeps every voxel tensor at the row
+    capacity B * NPOINT_LIST[0] with the live count on the device, the head follows it and
+    Detector3DTemplate.post_processing_static needs no host read either, so the whole chain is captured once; a call is
+    a copy into the static point buffer plus one replay.  That the capture succeeds is itself the check that no host
+    read is left on the path.
+
+    Every frame must hold exactly points_per_frame points (the reference's sample_points pads by resampling): points is
+    (batch_size * points_per_frame, 1 + C) with the frame index in column 0, frames contiguous and ascending."""
+
+    def __init__(self, model, batch_size, points_per_frame, warmup=2, example=None):
+        """example: points to warm up and capture on (the buffer otherwise holds every point at the centre of the
+        range)."""
+        if model.training:
+            raise ValueError("GraphedPointDetector captures the inference forward: call model.eval() first")
+        self.model = model
+        self.batch_size, self.points_per_frame = int(batch_size), int(points_per_frame)
+        if self.batch_size < 1 or self.points_per_frame < 1:
+            raise ValueError("batch_size and points_per_frame must be positive")
+        self.num_features = 1 + int(model.dataset.point_feature_encoder.num_point_features)
+        if example is not None:
+            self._check(example)
+        self.device = next(model.parameters()).device
+        if self.device.type != 'cuda':
+            raise ValueError("GraphedPointDetector needs the model on a GPU")
+        rows = self.batch_size * self.points_per_frame
+        self.points = torch.zeros((rows, self.num_features), dtype=torch.float32, device=self.device)
+        self.points[:, 0] = torch.arange(self.batch_size, device=self.device).repeat_interleave(self.points_per_frame)
+        rng = torch.as_tensor([float(v) for v in model.dataset.point_cloud_range], device=self.device)
+        self.points[:, 1:4] = 0.5 * (rng[0:3] + rng[3:6])
+        if example is not None:
+            self.points.copy_(example, non_blocking=True)
+        self.out = None
+        # eager warm-up on a side stream (allocator pools, workspaces, MIOpen kernel selection, cached constants), then capture
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            for _ in range(max(int(warmup), 1)):
+                self._forward()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        torch.cuda.synchronize(self.device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = self._forward()
+
+    def _check(self, points):
+        want = (self.batch_size * self.points_per_frame, self.num_features)
+        if points.dim() != 2 or tuple(points.shape) != want:
+            raise ValueError("GraphedPointDetector was captured for %d frames of exactly %d points with %d columns: "
+                             "points must be %s, got %s (pad short frames by resampling)"
+                             % (self.batch_size, self.points_per_frame, self.num_features, want, tuple(points.shape)))
+
+    def _forward(self):
+        """The eager static path: what the graph holds.  Returns post_processing_static's dict plus voxel_num_valid
+        (device int64[1], live voxels of the backbone), static_flags (the backbone's device booleans) and the head's
+        flat predictions post_processing reads (batch_index, batch_cls_preds, batch_box_preds, cls_preds_normalized)."""
+        bd = {'points': self.points, 'batch_size': self.batch_size, 'static_caps': {}}
+        with torch.no_grad():
+            for m in self.model.module_list:
+                bd = m(bd)
+            out = dict(self.model.post_processing_static(bd))
+        out['voxel_num_valid'] = bd['voxel_num_valid']
+        out['static_flags'] = bd['static_flags']
+        out.update({k: bd[k] for k in ('batch_index', 'batch_cls_preds', 'batch_box_preds', 'cls_preds_normalized')})
+        out['batch_size'] = self.batch_size
+        return out
+
+    def __call__(self, points):
+        """Copies the batch in and replays.  Returns the static output dict (overwritten by the next call)."""
+        self._check(points)
+        self.points.copy_(points, non_blocking=True)
+        refresh_folded_bn(self.model)        # BatchNorm folds the graph captured: rebuilt in place if a parameter was written
+        refresh_graph_constants()            # likewise the packed weights it reads
+        self.graph.replay()
+        return self.out
+
+    def pred_dicts(self):
+        """The last call's detections as model.post_processing returns them: a list of {'pred_boxes', 'pred_scores',
+        'pred_labels'} per frame.  One host read (counts and flags); a False flag raises, the results of such a batch
+        are meaningless."""
+        st = self.out
+        names = ['post-processing layout_ok'] + ['backbone ' + k for k in sorted(st['static_flags'])]
+        flags = [st['layout_ok']] + [st['static_flags'][k] for k in sorted(st['static_flags'])]
+        host = torch.cat([st['count'].to(torch.int64)] + [f.to(torch.int64).view(1) for f in flags]).tolist()
+        b = self.batch_size
+        bad = [n for n, v in zip(names, host[b:]) if not v]
+        if bad:
+            raise RuntimeError("GraphedPointDetector: the batch broke the static path's contract (%s is False): frames "
+                               "must be equal, contiguous and ascending, and every sampled point inside "
+                               "POINT_CLOUD_RANGE" % ", ".join(bad))
+        return [{'pred_boxes': st['pred_boxes'][i, :host[i]], 'pred_scores': st['pred_scores'][i, :host[i]],
+                 'pred_labels': st['pred_labels'][i, :host[i]]} for i in range(b)]
+
+
 class GraphedTrainStep(object):
     """Forward + backward of one training step as ONE hipGraph replay (single process; data-parallel ranks stay eager: DDP's
     bucket hooks and the RCCL all-reduce are not captured here).

@@ -10,6 +10,15 @@ of each MLP (BatchNorm2d, ReLU, ...) runs unchanged on the result.
 
 Deliberate differences: the device of the voxel-size / range tensors follows the inputs (the reference hard-codes
 'cuda:0'), and torch.arange replaces the deprecated torch.range (same values).
+
+Static mode (forward(..., static=True) at layer 0; later layers follow sp_tensor.n_valid): inference with no host read,
+so that the whole forward can be captured in a graph.  The voxel tensors keep a row CAPACITY (B * npoint of layer 0) and
+the live row count stays on the device in sp_tensor.n_valid: of scores, centroids, centroid_voxel_idxs and
+sp_tensor.features / .indices only the first n_valid rows are live, the rest hold whatever the buffers held.  The cell
+table and the sparse update's per-voxel mean come from spx.ops.voxel_table_build / voxel_rows_mean (include/spx.h §19),
+which never read a dead row; row-local torch modules (confidence_mlp, the ori_scores product) compute on dead rows too,
+and nothing reduces over them.  A sampled point outside the grid gets voxel row -1 in unique_idxs (the backbone reports
+it in static_flags); the eager path would have failed on it.
 """
 from functools import partial
 from typing import List
@@ -23,8 +32,17 @@ from . import pointnet2_utils
 from ..pointnet2_stack import voxel_query_utils
 from ....utils import common_utils, voxel_aggregation_utils
 from ....utils.spconv_utils import replace_feature, spconv
+from spx import ops as spx_ops
 
 __all__ = ["VoxelPointnetSAModuleFSMSGDistillation", "VoxelPointnetSAModuleFSDistillation"]
+
+
+_stage_hook = None    # callable(name) or None: a profiler's marker at the END of each stage (tools/point_head_bench.py)
+
+
+def _stage(name):
+    if _stage_hook is not None:
+        _stage_hook(name)
 
 
 def _conv_weight(conv):
@@ -58,9 +76,14 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
         self.point_cloud_range = []
 
     def _grid_tensors(self, device):
-        """(voxel_size, point_cloud_range) as float32 tensors on `device`."""
-        return (torch.tensor(self.voxel_size, device=device).float(),
-                torch.tensor(self.point_cloud_range, device=device).float())
+        """(voxel_size, point_cloud_range) as float32 tensors on `device`, built once per device and setting: the
+        host-to-device copy behind torch.tensor(list) cannot be captured in a graph."""
+        key = (device, tuple(float(v) for v in self.voxel_size), tuple(float(v) for v in self.point_cloud_range))
+        cache = self.__dict__.setdefault('_grid_cache', {})
+        if key not in cache:
+            cache[key] = (torch.tensor(self.voxel_size, device=device).float(),
+                          torch.tensor(self.point_cloud_range, device=device).float())
+        return cache[key]
 
     # ------------------------------------------------------------------------------------------- sampling
     def _sample(self, xyz, features, scores, batch_size):
@@ -101,6 +124,7 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
             else:
                 raise NotImplementedError
             sample_idx_list.append(sample_idx + lo)
+            _stage('sample:' + method)
         return torch.cat(sample_idx_list, dim=-1)
 
     # ------------------------------------------------------------------------------------------- groupers
@@ -112,6 +136,7 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
                                                               xyz, new_xyz)
         else:
             idx_cnt, idx = pointnet2_utils.ball_query(grouper.radius, grouper.nsample, xyz, new_xyz)
+        _stage('ball_query')
         batch_size, n, _ = xyz.shape
         npoint = new_xyz.shape[1]
         rows = idx + (torch.arange(batch_size, device=idx.device, dtype=idx.dtype) * n).view(-1, 1, 1)
@@ -137,6 +162,7 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
         else:
             idx, empty_ball_mask, _ = voxel_query_utils.voxel_query(grouper.max_range, grouper.radius, grouper.nsample,
                                                                     voxel_xyz, ctr, point_grid_coords, v2p_ind_tensor)
+        _stage('voxel_query')
         batch_size = new_xyz.shape[0]
         yf = pointnet2_utils.group_project(features_in, _conv_weight(self.point_mlps[i][0]), None, voxel_xyz, ctr, idx,
                                            empty_ball_mask, batch_size)
@@ -146,18 +172,25 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
 
     # ------------------------------------------------------------------------------------------- forward
     def forward(self, xyz: torch.Tensor, features: torch.Tensor = None, new_xyz=None, scores=None, part_scores=None,
-                sp_tensor=None, unique_idxs=None, switch=False, centroids=None, centroid_voxel_idxs=None):
+                sp_tensor=None, unique_idxs=None, switch=False, centroids=None, centroid_voxel_idxs=None, static=False):
         """
         :param xyz: (B, N, 3) tensor of the xyz coordinates of the features
         :param features: (B, C, N) tensor of the descriptors of the features
         :param new_xyz: (B, npoint, 3) centres, or None to sample them
         :param scores: (N', 3) confidence logits of the previous layer's voxels, required when using s-fps
         :param sp_tensor / centroids / centroid_voxel_idxs / unique_idxs: the previous layer's voxel aggregation
+        :param static: layer 0 only: aggregate at static row capacity with no host read (module docstring); later
+                 layers take the mode from sp_tensor.n_valid
         :return: new_xyz (B, npoint, 3), new_features (B, C', npoint), new_scores or None, sp_tensor, centroids,
                  centroid_voxel_idxs, unique_idxs, None
         """
         new_features_list = []
         batch_size = len(xyz)
+        static = bool(static) if sp_tensor is None else sp_tensor.n_valid is not None
+        if static and (self.training or torch.is_grad_enabled()):
+            raise RuntimeError('the static-capacity path of the voxel-point SA modules is inference only: it needs '
+                               'model.eval() and torch.no_grad() (training %s, grad %s)'
+                               % (self.training, torch.is_grad_enabled()))
         ori_scores = None
         old_features = None
         voxel_size_tensor, point_cloud_range_tensor = self._grid_tensors(xyz.device)
@@ -181,7 +214,11 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
             unique_idxs = unique_idxs[sample_idx.view(-1).long()]
 
         if sp_tensor is not None:
-            v2p_ind_tensor = common_utils.generate_voxel2pinds(sp_tensor)
+            if static:
+                v2p_ind_tensor = spx_ops.voxel_table_build(sp_tensor.indices, sp_tensor.batch_size,
+                                                           sp_tensor.spatial_shape, d_n=sp_tensor.n_valid)
+            else:
+                v2p_ind_tensor = common_utils.generate_voxel2pinds(sp_tensor)
             num_points = new_xyz.shape[1]
             pgc = new_xyz.clone().view(-1, 3)
             pgc_x = (pgc[:, 0:1] - point_cloud_range_tensor[0]) / voxel_size_tensor[0]
@@ -193,6 +230,7 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
             # the centroids' xyz columns only lead back to sampled coordinates, which carry no gradient
             voxel_xyz = centroids[:, 1:4].detach().contiguous()
             features_in = sp_tensor.features.contiguous()
+            _stage('voxel_table')
 
         for i in range(len(self.groupers)):
             if sp_tensor is None:
@@ -211,12 +249,14 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
             else:
                 raise NotImplementedError
             new_features_list.append(pooled_features.squeeze(-1))  # (B, mlp[-1], npoint)
+            _stage('mlp_pool')
 
         if self.skip_connection and old_features is not None:
             new_features_list.append(old_features)
         new_features = torch.cat(new_features_list, dim=1)
         if self.aggregation_mlp is not None:
             new_features = self.aggregation_mlp(new_features)
+        _stage('mlp_pool')
 
         if sp_tensor is None:
             batch_size, channel, num_points = new_features.shape
@@ -229,16 +269,27 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
             xyz_for_voxel = torch.cat([batch_idx.to(new_xyz.dtype), new_xyz.view(-1, 3)], dim=-1)
             features_for_voxel = new_features.permute(0, 2, 1).contiguous().view(-1, channel)
             point_for_voxel = torch.cat([xyz_for_voxel, features_for_voxel], dim=-1)   # bxyz + features
-            centroids_coords_features, centroid_voxel_idxs, _, unique_idxs = \
-                voxel_aggregation_utils.get_centroid_per_voxel(point_for_voxel, voxel_idxs)
             sparse_shape = np.asarray(self.grid_size)[::-1].astype(np.int64)
+            if static:
+                # B * npoint rows, as many as there are points: no overflow; the live count stays on the device
+                centroids_coords_features, centroid_voxel_idxs, _, unique_idxs, n_valid = \
+                    voxel_aggregation_utils.get_centroid_per_voxel(
+                        point_for_voxel, voxel_idxs, extent=[batch_size] + [int(v) for v in sparse_shape], sync=False)
+                static_kw = dict(n_valid=n_valid, static_caps={})
+            else:
+                centroids_coords_features, centroid_voxel_idxs, _, unique_idxs = \
+                    voxel_aggregation_utils.get_centroid_per_voxel(point_for_voxel, voxel_idxs)
+                static_kw = {}
             centroids = centroids_coords_features[:, 0:4].contiguous()
             sp_tensor = spconv.SparseConvTensor(features=centroids_coords_features[:, 4:].contiguous(),
                                                 indices=centroid_voxel_idxs.int(), spatial_shape=sparse_shape,
-                                                batch_size=batch_size)
+                                                batch_size=batch_size, **static_kw)
+            _stage('centroid_aggregation')
         elif self.sa_layer_idx > 0 and self.sa_layer_idx < 3:
             sp_tensor = self._unet_update(new_xyz, new_features, sp_tensor, centroid_voxel_idxs, ori_scores,
-                                          voxel_size_tensor, point_cloud_range_tensor)
+                                          voxel_size_tensor, point_cloud_range_tensor,
+                                          v2p_ind_tensor if static else None)
+            _stage('unet')
 
         if self.confidence_mlp is not None:
             new_scores = self.confidence_mlp(sp_tensor.features.unsqueeze(-1)).squeeze(2)
@@ -247,10 +298,42 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
         return new_xyz.contiguous(), new_features.contiguous(), None, \
             sp_tensor, centroids, centroid_voxel_idxs.contiguous(), unique_idxs, None
 
+    def _unet_source_static(self, new_xyz, new_features, sp_tensor, centroid_voxel_idxs, table):
+        """The U-Net's input at static capacity: the per-voxel mean of the new point features at the rows of sp_tensor,
+        one op instead of the eager chain below (same live rows, bit for bit; dead rows are not written)."""
+        feats = spx_ops.voxel_rows_mean(new_xyz, new_features, table, self.point_cloud_range[0:3], self.voxel_size,
+                                        sp_tensor.features.shape[0], d_n_rows=sp_tensor.n_valid)
+        return spconv.SparseConvTensor(features=feats, indices=centroid_voxel_idxs.int(),
+                                       spatial_shape=sp_tensor.spatial_shape, batch_size=new_xyz.shape[0],
+                                       n_valid=sp_tensor.n_valid, static_caps=sp_tensor.static_caps)
+
     def _unet_update(self, new_xyz, new_features, sp_tensor, centroid_voxel_idxs, ori_scores, voxel_size_tensor,
-                     point_cloud_range_tensor):
+                     point_cloud_range_tensor, static_table=None):
         """Layers 1-2: aggregate the new point features into the voxels of sp_tensor, run the sparse U-Net on them and
-        add the result, weighted by the previous layer's confidence, to sp_tensor's own 1x1 update."""
+        add the result, weighted by the previous layer's confidence, to sp_tensor's own 1x1 update.
+        static_table: sp_tensor's cell table in static mode (sp_tensor.n_valid is the live row count)."""
+        if static_table is not None:
+            source_tensor = self._unet_source_static(new_xyz, new_features, sp_tensor, centroid_voxel_idxs, static_table)
+        else:
+            source_tensor = self._unet_source(new_xyz, new_features, sp_tensor, centroid_voxel_idxs, voxel_size_tensor,
+                                              point_cloud_range_tensor)
+        _stage('unet_source')
+        sp4x_tensor = self.spconv4x_mlps(source_tensor)
+        sp8x_tensor = self.spconv8x_mlps(sp4x_tensor)
+        sp16x_tensor = self.spconv16x_mlps(sp8x_tensor)
+        spinv16x_tensor = self.spconvinv16x_mlps(sp16x_tensor)
+        spinv16x_tensor = replace_feature(spinv16x_tensor, spinv16x_tensor.features + sp16x_tensor.features)
+        spinv8x_tensor = self.spconvinv8x_mlps(spinv16x_tensor)
+        spinv8x_tensor = replace_feature(spinv8x_tensor, spinv8x_tensor.features + sp8x_tensor.features)
+        spinv4x_tensor = self.spconvinv4x_mlps(spinv8x_tensor)
+        spinv4x_tensor = replace_feature(spinv4x_tensor, spinv4x_tensor.features + sp4x_tensor.features)
+        dest_tensor = self.spconv_out_mlps(spinv4x_tensor)
+        sp_tensor = self.spconv_mlps(sp_tensor)
+        return replace_feature(sp_tensor, self.update_relu(sp_tensor.features + ori_scores * dest_tensor.features))
+
+    def _unet_source(self, new_xyz, new_features, sp_tensor, centroid_voxel_idxs, voxel_size_tensor,
+                     point_cloud_range_tensor):
+        """The U-Net's input: the per-voxel mean of the new point features at the rows of sp_tensor, zeros elsewhere."""
         batch_size, last_channel, num_points = new_features.shape
         new_point_idxs = voxel_aggregation_utils.get_voxel_indices(new_xyz.view(-1, 3), voxel_size=voxel_size_tensor,
                                                                    point_cloud_range=point_cloud_range_tensor)
@@ -266,21 +349,8 @@ class _VoxelPointnetSAModuleFSDistillationBase(nn.Module):
             voxel_aggregation_utils.get_nonempty_voxel_feature_indices(new_centroid_voxel_idxs, sp_tensor)
         source_features = new_centroids.new_zeros([sp_tensor.features.shape[0], new_centroids.shape[1] - 4])
         source_features[update_indices_nonempty] = new_centroids[:, 4:][update_nonempty_mask]
-        source_tensor = spconv.SparseConvTensor(features=source_features.contiguous(),
-                                                indices=centroid_voxel_idxs.int(),
-                                                spatial_shape=sp_tensor.spatial_shape, batch_size=batch_size)
-        sp4x_tensor = self.spconv4x_mlps(source_tensor)
-        sp8x_tensor = self.spconv8x_mlps(sp4x_tensor)
-        sp16x_tensor = self.spconv16x_mlps(sp8x_tensor)
-        spinv16x_tensor = self.spconvinv16x_mlps(sp16x_tensor)
-        spinv16x_tensor = replace_feature(spinv16x_tensor, spinv16x_tensor.features + sp16x_tensor.features)
-        spinv8x_tensor = self.spconvinv8x_mlps(spinv16x_tensor)
-        spinv8x_tensor = replace_feature(spinv8x_tensor, spinv8x_tensor.features + sp8x_tensor.features)
-        spinv4x_tensor = self.spconvinv4x_mlps(spinv8x_tensor)
-        spinv4x_tensor = replace_feature(spinv4x_tensor, spinv4x_tensor.features + sp4x_tensor.features)
-        dest_tensor = self.spconv_out_mlps(spinv4x_tensor)
-        sp_tensor = self.spconv_mlps(sp_tensor)
-        return replace_feature(sp_tensor, self.update_relu(sp_tensor.features + ori_scores * dest_tensor.features))
+        return spconv.SparseConvTensor(features=source_features.contiguous(), indices=centroid_voxel_idxs.int(),
+                                       spatial_shape=sp_tensor.spatial_shape, batch_size=batch_size)
 
 
 class VoxelPointnetSAModuleFSMSGDistillation(_VoxelPointnetSAModuleFSDistillationBase):

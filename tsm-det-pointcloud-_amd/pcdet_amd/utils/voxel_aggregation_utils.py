@@ -47,18 +47,30 @@ class _CentroidMean(torch.autograd.Function):
         return grad[inverse] / counts[inverse].to(grad.dtype).unsqueeze(-1), None, None, None
 
 
-def get_centroid_per_voxel(points, voxel_idxs, num_points_in_voxel=None):
+def get_centroid_per_voxel(points, voxel_idxs, num_points_in_voxel=None, extent=None, sync=True):
     """points (N, 4 + f) [bxyz + f], voxel_idxs (N, 4) non-negative ints -> centroids (N', 4 + f), their voxel indices
     (N', 4) in torch.unique(dim=0) order, rows merged per voxel (N', torch.unique's counts in both modes, as the
     reference returns them), and each point's voxel row (N)  (reference :132-161).
-    With `num_points_in_voxel` the mean is weighted by it (centroids of centroids)."""
+    With `num_points_in_voxel` the mean is weighted by it (centroids of centroids).
+
+    extent: the grid (e0, e1, e2, e3) that holds every index, when the caller knows it; without it the largest index
+    of each column is read from the device (one host sync).  The voxel order is lexicographic in the four columns, so
+    it does not depend on the extent; an index outside a given extent drops its point (voxel row -1).
+    sync=False (static capacity, needs `extent`): no host read.  Returns (centroids (N, 4 + f), voxel indices (N, 4),
+    None, voxel rows (N), d_n): only the first d_n (device int64[1]) rows of the first two are live, the rest hold
+    whatever the buffers held.  Inference only."""
     assert points.shape[0] == voxel_idxs.shape[0]
     n, c = points.shape
-    if n == 0:
+    if not sync:
+        assert extent is not None and n > 0, "sync=False needs the grid extent and at least one point"
+        assert not (points.requires_grad and torch.is_grad_enabled()), "sync=False is inference only"
+    elif n == 0:
         z = voxel_idxs.new_zeros((0,), dtype=torch.int64)
         return points.new_zeros((0, c)), voxel_idxs.new_zeros((0, 4)), z, z
     idx_f = voxel_idxs.to(torch.float32)
-    extent = (voxel_idxs.amax(dim=0) + 1).tolist()           # one host sync: the unit grid that holds every index
+    if extent is None:
+        extent = (voxel_idxs.amax(dim=0) + 1).tolist()       # one host sync: the unit grid that holds every index
+    extent = [int(e) for e in extent]
     assert max(extent) < (1 << 24), "indices must be exactly representable in fp32"
     pts = points.to(torch.float32)
     if num_points_in_voxel is not None:
@@ -68,15 +80,20 @@ def get_centroid_per_voxel(points, voxel_idxs, num_points_in_voxel=None):
         payload = pts
     table = torch.cat((idx_f, payload), dim=1).contiguous()   # [c0, c1, c2, c3, payload...]
     out = ops.dynamic_voxelize(table, [0.0, 0.0, 0.0, float(extent[1]), float(extent[2]), float(extent[3])],
-                               [1.0, 1.0, 1.0], batch_size=int(extent[0]), batch_col=0, xyz_col=1)
+                               [1.0, 1.0, 1.0], batch_size=int(extent[0]), batch_col=0, xyz_col=1, sync=sync)
     means = out["features"][:, 3:]                            # the three leading columns are the cell's own indices
     inverse = out["inverse"].long()
-    counts = torch.bincount(inverse, minlength=means.shape[0])
     if num_points_in_voxel is not None:
         centroids = means[:, :c] / means[:, c:c + 1]          # (sum p*w / m) / (sum w / m)
     else:
         centroids = means
+    if not sync:
+        # the same columns as below, without a host-built index tensor (its upload cannot be captured in a graph)
+        coords = out["coords"]
+        cells = torch.cat((coords[:, :1], coords[:, 1:].flip(1)), dim=1).to(voxel_idxs.dtype)
+        return centroids, cells, None, inverse, out["d_num_voxels"]
     cells = out["coords"][:, [0, 3, 2, 1]].to(voxel_idxs.dtype)   # kernel returns (c0, c3, c2, c1)
+    counts = torch.bincount(inverse, minlength=means.shape[0])
     if points.requires_grad and torch.is_grad_enabled():
         assert num_points_in_voxel is None, "the weighted mean carries no gradient"
         centroids = _CentroidMean.apply(points, centroids.to(points.dtype), inverse, counts)

@@ -160,6 +160,10 @@ SIGNATURES = {
                                                _sz, _vp]),
     "spx_stack_furthest_point_sample_ws_bytes": (_sz, [_i64]),
     "spx_stack_furthest_point_sample": (_int, [_vp, _vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "spx_voxel_table_build": (_int, [_vp, _i64, _vp, ctypes.c_int32, _i32p, _vp, _vp, _vp]),
+    "spx_voxel_rows_mean_ws_bytes": (_sz, [ctypes.c_int32, _i64]),
+    "spx_voxel_rows_mean": (_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _i32p, _f32p, _f32p, _vp, _i64, _vp,
+                                   _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1573,3 +1573,68 @@ def stack_furthest_point_sample(xyz, xyz_batch_cnt, npoint, total):
         check(lib.spx_stack_furthest_point_sample(_ptr(xyz), _ptr(nc), _ptr(npt), nc.shape[0], n, int(total), _ptr(idx),
                                                   _ptr(ws), wsb, _stream(xyz)), "spx_stack_furthest_point_sample")
     return idx
+
+
+# ------------------------------------------------------------------------- voxel rows at static capacity (§19)
+
+VOXEL_ROWS_MAX_M = 4096   # points per frame spx_voxel_rows_mean takes
+
+
+def _d_n(name, d_n, dev):
+    """An optional live row count: int64[1] on `dev`."""
+    if d_n is None:
+        return None
+    if not isinstance(d_n, torch.Tensor) or d_n.dtype != torch.int64 or d_n.numel() != 1 or d_n.device != dev:
+        raise _lib.SpxError("%s must be one int64 on %s" % (name, dev))
+    return d_n.contiguous()
+
+
+def voxel_table_build(indices, batch_size, spatial_shape, d_n=None):
+    """spx_voxel_table_build: indices (cap, 4) int32 (b, z, y, x), d_n the device live row count (None: every row is
+    live) -> table (B, Z, Y, X) int32, the row of the live voxel at each cell, -1 elsewhere.  Rows at or beyond d_n are
+    never read; a live row outside the grid is skipped and raises SPX_ERR_OUT_OF_GRID in the sticky status word
+    (check_status).  No host read."""
+    _need_gpu(indices, d_n)
+    lib = _lib.load()
+    if indices.dim() != 2 or indices.shape[1] != 4 or indices.dtype != torch.int32:
+        raise _lib.SpxError("voxel_table_build: indices must be (cap, 4) int32, got %s %s"
+                            % (tuple(indices.shape), indices.dtype))
+    indices = indices.contiguous()
+    dev = indices.device
+    d_n = _d_n("voxel_table_build: d_n", d_n, dev)
+    shape = [int(s) for s in spatial_shape]
+    table = torch.empty([int(batch_size)] + shape, dtype=torch.int32, device=dev)
+    if indices.shape[0] == 0:
+        return table.fill_(-1)
+    check(lib.spx_voxel_table_build(_ptr(indices), indices.shape[0], _ptr(d_n), int(batch_size), i3(shape), _ptr(table),
+                                    _ptr(status_word(dev)), _stream(indices)), "spx_voxel_table_build")
+    return table
+
+
+def voxel_rows_mean(new_xyz, feats, table, range_lo, voxel_size, cap, d_n_rows=None, out=None):
+    """spx_voxel_rows_mean: new_xyz (B, m, 3), feats (B, C, m) channels first, table (B, Z, Y, X) of voxel_table_build,
+    range_lo / voxel_size 3 host floats (x, y, z) -> out (cap, C): the per-cell mean of the feature columns over each
+    frame's points, at the table's row of the cell; the other rows below the live count d_n_rows (None: cap) are 0,
+    rows at or beyond it are not written (they keep what a caller's `out` (cap, C) held).  Deterministic, no host read."""
+    _need_gpu(new_xyz, feats, table, d_n_rows)
+    lib = _lib.load()
+    if new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or feats.dim() != 3 or feats.shape[0] != new_xyz.shape[0] \
+            or feats.shape[2] != new_xyz.shape[1] or table.dim() != 4 or table.shape[0] != new_xyz.shape[0] \
+            or table.dtype != torch.int32:
+        raise _lib.SpxError("voxel_rows_mean: new_xyz %s, feats %s, table %s %s do not match (B, m, 3), (B, C, m), "
+                            "(B, Z, Y, X) int32" % (tuple(new_xyz.shape), tuple(feats.shape), tuple(table.shape),
+                                                    table.dtype))
+    new_xyz, feats, table = _f32(new_xyz), _f32(feats), table.contiguous()
+    dev = feats.device
+    d_n_rows = _d_n("voxel_rows_mean: d_n_rows", d_n_rows, dev)
+    b, c, m = feats.shape
+    if out is None:
+        out = torch.empty((int(cap), c), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (int(cap), c) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise _lib.SpxError("voxel_rows_mean: out must be a contiguous float32 (%d, %d) on %s" % (int(cap), c, dev))
+    wsb = lib.spx_voxel_rows_mean_ws_bytes(b, m)
+    ws = workspace(dev, wsb)
+    check(lib.spx_voxel_rows_mean(_ptr(new_xyz), _ptr(feats), b, c, m, _ptr(table), i3(table.shape[1:]), f_arr(range_lo),
+                                  f_arr(voxel_size), _ptr(d_n_rows), int(cap), _ptr(out), _ptr(ws), wsb, _stream(feats)),
+          "spx_voxel_rows_mean")
+    return out
