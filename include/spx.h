@@ -878,6 +878,41 @@ int spx_voxel_rows_mean(const float *new_xyz, const float *feats, int32_t batch,
                         const int32_t *table, const int32_t *shape3, const float *range_lo3, const float *voxel_size3,
                         const int64_t *d_n_rows, int64_t cap, float *out, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 20. Centre-head target assignment without a host read (csrc/center_targets.hip)
+ *    replaces: CenterHead.assign_targets / assign_target_of_single_head (reference
+ *      pcdet/models/dense_heads/center_head.py:103-219) with gaussian_radius and draw_gaussian_to_heatmap
+ *      (pcdet/models/model_utils/centernet_utils.py:9-69): a Python loop over heads x frames x boxes with a copy of every
+ *      frame's boxes to the host, radius[k].item() per box and a numpy Gaussian per box.
+ *    Two launches for the whole batch and every head, on the given stream; EVERY output element is written, each by one
+ *    thread, and overlapping Gaussians combine by max: no atomics, bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* gt_boxes [b, m, ld], ld >= 8, columns [x, y, z, dx, dy, dz, rz, (extra ...), class]; the class is the LAST column,
+ *   1-based over the detector's classes, 0 on padding rows (may be NULL when m == 0).  gt_boxes is never written.
+ * class_to_head_slot: DEVICE int32 [num_class + 1, 2] = (head, 1-based class within the head) of a global class id, -1
+ *   for a class no head owns; (int)class outside 1..num_class owns nothing.  head_channels: HOST int32 [n_heads], the
+ *   classes of each head; n_heads <= 16 else SPX_ERR_UNSUPPORTED.  range_lo2, voxel_size2: HOST float[2] (x, y).
+ * Slot k of (head, frame) = the k-th of the frame's boxes owned by the head, in input order; boxes at k >= num_max_objs
+ *   are dropped.  coord = ((x - lo) / vs) / stride in float, rounded after every operation, clamped to [0, w - 0.5] and
+ *   [0, h - 0.5]; cell = (int)coord.  radius = max((int)gaussian_radius((dx / vs0) / stride, (dy / vs1) / stride,
+ *   gaussian_overlap), min_radius) in float in the reference's operation order, sqrt correctly rounded.  A slot whose
+ *   scaled dx or dy is not > 0 keeps its place with mask 0 and zeros and draws nothing.
+ * Outputs, head after head in one buffer each (c_j = head_channels[j], off_j = c_0 + ... + c_(j-1), K = num_max_objs):
+ *   heatmaps: head j at b * h * w * off_j floats, [b, c_j, h, w]: the maximum over the live slots of the (frame, head)
+ *     with class channel c of exp(-(ddx^2 + ddy^2) / (2 s^2)), s = (2 r + 1) / 6, inside the window |ddx|, |ddy| <= r
+ *     around the cell, evaluated in double and rounded once (the centre is exactly 1), 0 elsewhere;
+ *   target_boxes [n_heads, b, K, ld] = [coord - cell (2), z, logf(dx, dy, dz), cosf(rz), sinf(rz), columns 7 .. ld - 2];
+ *   inds [n_heads, b, K] int64 = cell_y * w + cell_x; masks [n_heads, b, K] int64 = 1 on live slots; zeros elsewhere.
+ * ws: spx_center_assign_targets_ws_bytes bytes. */
+size_t spx_center_assign_targets_ws_bytes(int32_t b, int32_t n_heads, int64_t num_max_objs);
+int spx_center_assign_targets(const float *gt_boxes, int32_t b, int64_t m, int32_t ld, const int32_t *class_to_head_slot,
+                              int32_t num_class, int32_t n_heads, const int32_t *head_channels, const float *range_lo2,
+                              const float *voxel_size2, float feature_map_stride, int32_t w, int32_t h,
+                              int64_t num_max_objs, double gaussian_overlap, int32_t min_radius, float *heatmaps,
+                              float *target_boxes, int64_t *inds, int64_t *masks, void *ws, size_t ws_bytes,
+                              spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,13 @@
 from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
+from .center_head import CenterHead
 from .point_head_template import PointHeadTemplate
 from .point_head_vote_sasa_statistic_distillation import PointHeadVoteSASAStatisticDistillation
 
 __all__ = {
     'AnchorHeadTemplate': AnchorHeadTemplate,
     'AnchorHeadSingle': AnchorHeadSingle,
+    'CenterHead': CenterHead,
     'PointHeadTemplate': PointHeadTemplate,
     'PointHeadVoteSASAStatisticDistillation': PointHeadVoteSASAStatisticDistillation,
 }

@@ -1,3 +1,4 @@
+from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .point_3dssd import Point3DSSD
 from .second_net import SECONDNet
@@ -6,6 +7,7 @@ __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'SECONDNet': SECONDNet,
     '3DSSD': Point3DSSD,
+    'CenterPoint': CenterPoint,
 }
 
 

@@ -156,3 +156,62 @@ class PointSASALoss(nn.Module):
             li_loss = self.loss_func(li_scores.expand_as(one_hot)[None], one_hot[None], cls_weights.reshape(1, -1))
             l_loss.append(self.layer_weights[i] * li_loss.sum() / torch.clamp(cls_weights.sum(dim=0), min=1.0))
         return l_loss
+
+
+# ------------------------------------------------------------------ centre head (reference loss_utils.py:420-542)
+
+def neg_loss_cornernet(pred, gt, mask=None):
+    """CornerNet's penalty-reduced focal loss: pred, gt (B, C, H, W), pred a probability, gt 1 exactly at the centres;
+    mask (B, H, W) or None -> 0-d.  The value of the reference, which branches on `num_pos == 0` on the host; here the
+    two branches are selected on the device, so the loss can be captured in a graph."""
+    pos_inds = gt.eq(1).float()
+    neg_inds = gt.lt(1).float()
+    neg_weights = torch.pow(1 - gt, 4)
+    pos_loss = torch.log(pred) * torch.pow(1 - pred, 2) * pos_inds
+    neg_loss = torch.log(1 - pred) * torch.pow(pred, 2) * neg_weights * neg_inds
+    if mask is not None:
+        mask = mask[:, None, :, :].float()
+        pos_loss = pos_loss * mask
+        neg_loss = neg_loss * mask
+        num_pos = (pos_inds.float() * mask).sum()
+    else:
+        num_pos = pos_inds.float().sum()
+    pos_loss = pos_loss.sum()
+    neg_loss = neg_loss.sum()
+    return torch.where(num_pos == 0, -neg_loss, -(pos_loss + neg_loss) / num_pos.clamp_min(1.0))
+
+
+class FocalLossCenterNet(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.neg_loss = neg_loss_cornernet
+
+    def forward(self, out, target, mask=None):
+        return self.neg_loss(out, target, mask=mask)
+
+
+def _reg_loss(regr, gt_regr, mask):
+    """L1 over the live slots: regr, gt_regr (B, K, D), mask (B, K) -> (D), each column's sum / max(#live, 1), with the
+    reference's NaN mask (a NaN target zeroes the prediction's side only, so it still surfaces in the loss)."""
+    num = mask.float().sum()
+    mask = mask.unsqueeze(2).expand_as(gt_regr).float()
+    isnotnan = (~torch.isnan(gt_regr)).float()
+    mask = mask * isnotnan
+    regr = regr * mask
+    gt_regr = gt_regr * mask
+    loss = torch.abs(regr - gt_regr)
+    loss = loss.transpose(2, 0)
+    loss = torch.sum(loss, dim=2)
+    loss = torch.sum(loss, dim=1)
+    return loss / torch.clamp_min(num, min=1.0)
+
+
+class RegLossCenterNet(nn.Module):
+    def forward(self, output, mask, ind=None, target=None):
+        """output (B, D, H, W) with ind (B, K) flat cells, or (B, K, D) without; mask (B, K); target (B, K, D) -> (D)."""
+        if ind is None:
+            pred = output
+        else:
+            from ..models.model_utils.centernet_utils import _transpose_and_gather_feat
+            pred = _transpose_and_gather_feat(output, ind)
+        return _reg_loss(pred, target, mask)

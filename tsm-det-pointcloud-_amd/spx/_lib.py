@@ -164,6 +164,10 @@ SIGNATURES = {
     "spx_voxel_rows_mean_ws_bytes": (_sz, [ctypes.c_int32, _i64]),
     "spx_voxel_rows_mean": (_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _i32p, _f32p, _f32p, _vp, _i64, _vp,
                                    _vp, _sz, _vp]),
+    "spx_center_assign_targets_ws_bytes": (_sz, [ctypes.c_int32, ctypes.c_int32, _i64]),
+    "spx_center_assign_targets": (_int, [_vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_int32,
+                                         _i32p, _f32p, _f32p, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _i64,
+                                         ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

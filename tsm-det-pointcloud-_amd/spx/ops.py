@@ -1638,3 +1638,54 @@ def voxel_rows_mean(new_xyz, feats, table, range_lo, voxel_size, cap, d_n_rows=N
                                   f_arr(voxel_size), _ptr(d_n_rows), int(cap), _ptr(out), _ptr(ws), wsb, _stream(feats)),
           "spx_voxel_rows_mean")
     return out
+
+
+# --------------------------------------------------------------------------------- centre-head target assignment (§20)
+
+def center_assign_targets(gt_boxes, class_to_head_slot, head_channels, point_cloud_range, voxel_size, feature_map_stride,
+                          feature_map_size, num_max_objs=500, gaussian_overlap=0.1, min_radius=2):
+    """spx_center_assign_targets: the targets of every head of a centre head for the whole batch, two launches, no host
+    read.  gt_boxes (B, M, C >= 8) fp32 device [x, y, z, dx, dy, dz, rz, (extra ...), class], the class in the LAST column,
+    1-based over the detector's classes, 0 on padding rows; class_to_head_slot: device int32 (num_class + 1, 2) = (head,
+    1-based class within the head) per global class id, -1 where no head owns it; head_channels: the classes of each head
+    (host ints); feature_map_size (W, H).  Returns a dict of per-head lists, dtypes and shapes as the reference's
+    assign_target_of_single_head stacked over the batch: heatmaps (B, C_h, H, W) fp32, target_boxes (B, num_max_objs, C)
+    fp32, inds and masks (B, num_max_objs) int64.  Slot k of a frame and head is the k-th of the frame's boxes owned by
+    the head, in input order.  gt_boxes is NOT written: the reference rewrites its class column in place while it filters
+    the boxes per head, so with several heads its later heads (and later modules) see corrupted labels; here every head
+    sees the original ones.  Deterministic (max of Gaussians, no atomics); the outputs are fully written by the call."""
+    _need_gpu(gt_boxes, class_to_head_slot)
+    lib = _lib.load()
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] < 8:
+        raise _lib.SpxError("center_assign_targets: gt_boxes %s is not (B, M, >= 8)" % (tuple(gt_boxes.shape),))
+    heads = [int(c) for c in head_channels]
+    if class_to_head_slot.dtype != torch.int32 or class_to_head_slot.dim() != 2 or class_to_head_slot.shape[1] != 2 \
+            or class_to_head_slot.shape[0] < 1 or class_to_head_slot.device != gt_boxes.device:
+        raise _lib.SpxError("center_assign_targets: class_to_head_slot %s %s is not int32 (num_class + 1, 2) on %s"
+                            % (tuple(class_to_head_slot.shape), class_to_head_slot.dtype, gt_boxes.device))
+    gt_boxes = _f32(gt_boxes)
+    table = class_to_head_slot.contiguous()
+    b, m, ld = gt_boxes.shape
+    w, h = int(feature_map_size[0]), int(feature_map_size[1])
+    k, n_heads, total = int(num_max_objs), len(heads), sum(heads)
+    dev = gt_boxes.device
+    heat = torch.empty((b * total * h * w,), dtype=torch.float32, device=dev)
+    boxes = torch.empty((n_heads, b, k, ld), dtype=torch.float32, device=dev)
+    inds = torch.empty((n_heads, b, k), dtype=torch.int64, device=dev)
+    masks = torch.empty((n_heads, b, k), dtype=torch.int64, device=dev)
+    if b > 0:
+        nbytes = lib.spx_center_assign_targets_ws_bytes(b, n_heads, k)
+        ws = workspace(dev, nbytes)
+        check(lib.spx_center_assign_targets(_ptr(gt_boxes) if m > 0 else None, b, m, ld, _ptr(table), table.shape[0] - 1,
+                                            n_heads, (ctypes.c_int32 * n_heads)(*heads),
+                                            f_arr([point_cloud_range[0], point_cloud_range[1]]),
+                                            f_arr([voxel_size[0], voxel_size[1]]), float(feature_map_stride), w, h, k,
+                                            float(gaussian_overlap), int(min_radius), _ptr(heat), _ptr(boxes), _ptr(inds),
+                                            _ptr(masks), _ptr(ws), nbytes, _stream(gt_boxes)),
+              "spx_center_assign_targets")
+    heatmaps, off = [], 0
+    for c in heads:
+        heatmaps.append(heat[b * h * w * off:b * h * w * (off + c)].view(b, c, h, w))
+        off += c
+    return {"heatmaps": heatmaps, "target_boxes": list(boxes.unbind(0)), "inds": list(inds.unbind(0)),
+            "masks": list(masks.unbind(0))}
