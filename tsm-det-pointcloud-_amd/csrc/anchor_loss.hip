@@ -88,7 +88,10 @@ __global__ __launch_bounds__(256) void k_anchor_loss(LossArgs g, const int32_t* 
       const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
       l_cls += aw * pt * pt * bce * wc;
       const float dpt = (1.f - 2.f * t) * p * (1.f - p);
-      dcls[o * g.NC + c] = aw * (2.f * pt * dpt * bce + pt * pt * (p - t)) * wc * invB * g.cls_w;
+      // d(bce)/dx = p - t, except at a logit of exactly 0, where the reference's autograd takes clamp(x, min=0)' = 1
+      // and |x|' = 0 and so arrives at 1 - t
+      const float dbce = (x == 0.f ? 1.f : p) - t;
+      dcls[o * g.NC + c] = aw * (2.f * pt * dpt * bce + pt * pt * dbce) * wc * invB * g.cls_w;
     }
     // ---- box regression: smooth L1 on the sin-difference code, weight (label > 0) / max(#pos, 1)
     const float wr = label > 0 ? norm : 0.f;
@@ -98,9 +101,16 @@ __global__ __launch_bounds__(256) void k_anchor_loss(LossArgs g, const int32_t* 
       float tg = g.tgt[o * 7 + k];
       float diff, dd = 1.f;
       if (k == 6) {
-        if (tg != tg) tg = pr;            // NaN targets are ignored (loss_utils.py:190)
-        diff = sinf(pr) * cosf(tg) - cosf(pr) * sinf(tg);
-        dd = cosf(pr) * cosf(tg) + sinf(pr) * sinf(tg);
+        // A NaN target is ignored (loss_utils.py:190) and a prediction equal to its target has no difference: exactly 0,
+        // as in the reference's unfused arithmetic.  Evaluated for tg == pr, sin(pr) cos(tg) - cos(pr) sin(tg) is
+        // contracted to fma(s, c, -(c * s)), the rounding residue of the product, which the L1 branch (beta < 1e-5)
+        // turns into a gradient of +-1.
+        if (tg != tg || tg == pr) {
+          diff = 0.f;
+        } else {
+          diff = sinf(pr) * cosf(tg) - cosf(pr) * sinf(tg);
+          dd = cosf(pr) * cosf(tg) + sinf(pr) * sinf(tg);
+        }
       } else {
         diff = (tg != tg) ? 0.f : pr - tg;
       }
@@ -123,7 +133,12 @@ __global__ __launch_bounds__(256) void k_anchor_loss(LossArgs g, const int32_t* 
     if (g.dir != nullptr) {
       const float rot_gt = g.tgt[o * 7 + 6] + g.anchors[a * 7 + 6];
       const float v = rot_gt - g.dir_offset;
-      const float off = v - floorf(v / kTwoPi + 0.f) * kTwoPi;
+      float off;
+      {   // limit_period in the reference's unfused arithmetic: with the product contracted into the subtraction a target
+          // three or more periods away lands one bin off at a bin boundary
+#pragma clang fp contract(off)
+        off = v - floorf(v / kTwoPi + 0.f) * kTwoPi;
+      }
       int bin = (int)floorf(off / (kTwoPi / (float)g.NB));
       bin = bin < 0 ? 0 : (bin > g.NB - 1 ? g.NB - 1 : bin);
       float lg[kMaxC], mx = -3.4e38f;
