@@ -913,6 +913,37 @@ int spx_center_assign_targets(const float *gt_boxes, int32_t b, int64_t m, int32
                               float *target_boxes, int64_t *inds, int64_t *masks, void *ws, size_t ws_bytes,
                               spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 21. Centre-head box decoding without a host read (csrc/center_decode.hip)
+ *    replaces, for one head and the whole batch: the sigmoid / exp over full maps, _topk (torch.topk per class, then
+ *      over C x K), the six _transpose_and_gather_feat passes and the masks of decode_bbox_from_heatmap (reference
+ *      pcdet/models/model_utils/centernet_utils.py:118-216, called from center_head.py:288-321).
+ *    1 launch when c h w <= 8192, 2 when ceil(c h w / 8192) <= floor(8192 / k) (both yamls), one more per further
+ *    factor floor(8192 / k).  No float atomics; bit-identical from call to call for every input bit pattern.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Inputs, fp32 NCHW on the device: hm [b, c, h, w], center [b, 2, h, w], center_z [b, 1, h, w], dim [b, 3, h, w],
+ *   rot [b, 2, h, w] (cos in channel 0, sin in channel 1), vel [b, 2, h, w] or NULL.  voxel_size2, range_lo2: HOST
+ *   float[2] (x, y); post_center_limit_range6: HOST float[6].
+ * Selection: per frame the k largest of the c h w values of hm AS GIVEN, by float value descending (-0 equals +0), equal
+ *   values lower flat index ci h w + y w + x first; output row j of a frame is the j-th of that order.  Which cells a
+ *   NaN selects is unspecified; every gather index is in range whatever hm holds.
+ * Decode of a selected cell, fp32, no contraction: xs = ((x + center_x) * stride) * voxel_size2[0] + range_lo2[0], ys
+ *   likewise; z and vel copied; dims = expf(dim) if raw else dim; angle = atan2f(sin, cos); score = 1 / (1 + expf(-v))
+ *   if raw else v.  keep = xs, ys, z >= limit[0:3] and <= limit[3:6] (inclusive), and score > score_thresh (strict) when
+ *   has_score_thresh.  raw == 0 is decode_bbox_from_heatmap itself; raw != 0 takes the head's logits and log sizes.
+ * Outputs, every element written on every call: boxes [b, k, 7 (9 with vel)], scores [b, k], labels [b, k] int32
+ *   (0-based channel), cells [b, k] int64 (y w + x), keep [b, k] uint8, count [b] int32 (rows kept).  Rows that are not
+ *   kept hold their decoded values.
+ * 1 <= k <= h w else SPX_ERR_INVALID_ARG; k > 1024, c h w >= 2^31 or b > 65535: SPX_ERR_TOO_LARGE.
+ * ws: spx_center_decode_ws_bytes bytes. */
+size_t spx_center_decode_ws_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int32_t k);
+int spx_center_decode(const float *hm, const float *center, const float *center_z, const float *dim, const float *rot,
+                      const float *vel, int32_t b, int32_t c, int32_t h, int32_t w, int32_t k, float feature_map_stride,
+                      const float *voxel_size2, const float *range_lo2, const float *post_center_limit_range6,
+                      float score_thresh, int has_score_thresh, int raw, float *boxes, float *scores, int32_t *labels,
+                      int64_t *cells, uint8_t *keep, int32_t *count, void *ws, size_t ws_bytes, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,11 @@ What differs, on purpose:
   * get_loss keeps 0-d tensors in tb_dict instead of .item() floats (the project's convention, anchor_head_template.py)
     and does not overwrite pred_dict['hm'] with its sigmoid; with the device-side branch of neg_loss_cornernet the whole
     of assign_targets + get_loss captures under torch.cuda.graph.
-  * forward also takes the fork's `encoded_bev_features` list, as AnchorHeadSingle does."""
+  * forward also takes the fork's `encoded_bev_features` list, as AnchorHeadSingle does.
+  * Opt-in (POST_PROCESSING.FUSED: True, or static mode: `static_caps` in the batch dict): the boxes come from
+    generate_predicted_boxes_static — spx.ops.center_decode (csrc/center_decode.hip) and spx.ops.point_post_process per
+    head, static capacity, no host read — instead of the reference's sigmoid / exp / two topk / six gathers and its
+    per-frame mask, NMS and cat.  Without the key the reference's eager composition runs, unchanged."""
 import copy
 
 import numpy as np
@@ -153,8 +157,66 @@ class CenterHead(nn.Module):
         tb_dict['rpn_loss'] = loss.detach()
         return loss, tb_dict
 
+    _FUSED_NMS_TYPES = {'nms_gpu': False, 'nms_normal_gpu': True}       # NMS_TYPE -> axis-aligned pair test
+
+    def generate_predicted_boxes_static(self, batch_size, pred_dicts):
+        """The boxes of the whole batch at static capacity with no host read (usable under torch.cuda.graph): per head
+        spx.ops.center_decode (top-K over the logits, gathers and decode in one op) and spx.ops.point_post_process
+        (class-agnostic NMS with NMS_PRE_MAXSIZE / NMS_POST_MAXSIZE), then each frame's survivors packed head after head.
+        Returns pred_boxes (B, cap, 7 | 9), pred_scores (B, cap), pred_labels (B, cap) int64 (1-based), count (B) int32,
+        zeros past count; cap = the heads' min(MAX_OBJ_PER_SAMPLE, NMS_POST_MAXSIZE) added up.  The K candidates are
+        the K largest LOGITS with equal values in flat-index order: the eager path's topk over the sigmoids agrees
+        wherever those are distinct and leaves the order among equal ones unspecified."""
+        from spx import ops
+        cfg = self.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        if nms.NMS_TYPE == 'circle_nms':
+            raise NotImplementedError('circle_nms is not implemented (the reference asserts it away as not checked); '
+                                      'use NMS_TYPE nms_gpu')
+        if nms.NMS_TYPE not in self._FUSED_NMS_TYPES:
+            raise NotImplementedError('generate_predicted_boxes_static: NMS_TYPE %s (nms_gpu and nms_normal_gpu only)'
+                                      % nms.NMS_TYPE)
+        with_vel = 'vel' in self.separate_head_cfg.HEAD_ORDER
+        parts = []
+        for idx, pred_dict in enumerate(pred_dicts):
+            dec = ops.center_decode(pred_dict['hm'], pred_dict['center'], pred_dict['center_z'], pred_dict['dim'],
+                                    pred_dict['rot'], pred_dict['vel'] if with_vel else None, cfg.MAX_OBJ_PER_SAMPLE,
+                                    self.feature_map_stride, self.voxel_size, self.point_cloud_range,
+                                    cfg.POST_CENTER_LIMIT_RANGE, cfg.SCORE_THRESH, raw=True)
+            boxes = dec['boxes'].flatten(0, 1)
+            scores = dec['scores'].masked_fill(dec['keep'] == 0, -1.0)      # dropped rows: below the threshold of 0
+            labels = self.class_id_mapping_each_head[idx][dec['labels'].long()] + 1
+            res = ops.point_post_process(scores.flatten(), labels.flatten(), boxes, batch_size, [0.0], nms.NMS_THRESH,
+                                         nms.NMS_PRE_MAXSIZE, nms.NMS_POST_MAXSIZE,
+                                         axis_aligned=self._FUSED_NMS_TYPES[nms.NMS_TYPE], per_class=False)
+            out_boxes = res['boxes']
+            if with_vel:
+                live = (res['sel'] >= 0).unsqueeze(-1).to(boxes.dtype)
+                out_boxes = torch.cat([out_boxes, boxes[res['sel'].clamp_min(0)][..., 7:9] * live], dim=-1)
+            parts.append((out_boxes, res['scores'], res['labels'], res['count']))
+        if len(parts) == 1:
+            boxes, scores, labels, count = parts[0]
+        else:       # a stable partition: every frame's live rows first, head after head
+            boxes, scores, labels = (torch.cat([p[i] for p in parts], dim=1) for i in range(3))
+            live = torch.cat([torch.arange(p[1].shape[1], device=p[3].device).unsqueeze(0) < p[3].unsqueeze(1)
+                              for p in parts], dim=1)
+            order = torch.argsort((~live).to(torch.uint8), dim=1, stable=True)
+            boxes = boxes.gather(1, order.unsqueeze(-1).expand(-1, -1, boxes.shape[-1]))
+            scores, labels = scores.gather(1, order), labels.gather(1, order)
+            count = torch.stack([p[3] for p in parts]).sum(0).to(torch.int32)
+        return {'pred_boxes': boxes, 'pred_scores': scores, 'pred_labels': labels, 'count': count}
+
+    @staticmethod
+    def _slice_static(static):
+        """The list of per-frame dicts from the static outputs: ONE host read (the counts)."""
+        counts = static['count'].tolist()
+        return [{'pred_boxes': static['pred_boxes'][i, :n], 'pred_scores': static['pred_scores'][i, :n],
+                 'pred_labels': static['pred_labels'][i, :n]} for i, n in enumerate(counts)]
+
     def generate_predicted_boxes(self, batch_size, pred_dicts):
         post_process_cfg = self.model_cfg.POST_PROCESSING
+        if post_process_cfg.get('FUSED', False):     # opt-in: the fused decode + NMS, one host read for the batch
+            return self._slice_static(self.generate_predicted_boxes_static(batch_size, pred_dicts))
         device = pred_dicts[0]['hm'].device
         post_center_limit_range = torch.tensor(post_process_cfg.POST_CENTER_LIMIT_RANGE, dtype=torch.float32,
                                                device=device)
@@ -227,7 +289,20 @@ class CenterHead(nn.Module):
                 feature_map_stride=data_dict.get('spatial_features_2d_strides', None))
         self.forward_ret_dict['pred_dicts'] = pred_dicts
 
-        if not self.training or self.predict_boxes_when_training:
+        static = not self.training and data_dict.get('static_caps', None) is not None
+        fused = static or bool(self.model_cfg.POST_PROCESSING.get('FUSED', False))
+        if fused and (not self.training or self.predict_boxes_when_training):
+            final = self.generate_predicted_boxes_static(data_dict['batch_size'], pred_dicts)
+            if static:
+                data_dict['final_box_static'] = final
+            if self.predict_boxes_when_training:        # already zero-padded to one shape: no reorder_rois_for_refining
+                data_dict['rois'] = final['pred_boxes']
+                data_dict['roi_scores'] = final['pred_scores']
+                data_dict['roi_labels'] = final['pred_labels']
+                data_dict['has_class_labels'] = True
+            elif not static:
+                data_dict['final_box_dicts'] = self._slice_static(final)
+        elif not self.training or self.predict_boxes_when_training:
             pred_dicts = self.generate_predicted_boxes(data_dict['batch_size'], pred_dicts)
             if self.predict_boxes_when_training:
                 rois, roi_scores, roi_labels = self.reorder_rois_for_refining(data_dict['batch_size'], pred_dicts)

@@ -119,6 +119,63 @@ class GraphedDetector(object):
         return self.model.post_processing(dict(self.out))
 
 
+class GraphedCenterPoint(GraphedDetector):
+    """Eval forward of CenterPoint WITH its box decoding, NMS and (optionally) recall counts as ONE hipGraph replay.
+
+    Same static point buffer, padding row, row capacities, warm-up and capture as GraphedDetector; in static mode the
+    centre head decodes through CenterHead.generate_predicted_boxes_static (spx.ops.center_decode +
+    spx.ops.point_post_process, no host read) and CenterPoint.post_processing_static adds the recall counts, so the
+    whole chain is captured.  That the capture succeeds is itself the check that no host read is left on the path.
+
+    max_gt > 0 keeps a static (batch_size, max_gt, gt_columns) ground-truth buffer, zero padded, and the graph then
+    holds spx.ops.recall_count as well: pass gt_boxes to the call."""
+
+    def __init__(self, model, batch_size, max_points, level_factors=None, warmup=2, max_gt=0, gt_columns=8):
+        device = next(model.parameters()).device
+        self.max_gt = int(max_gt)
+        self.gt_boxes = None
+        if self.max_gt > 0:
+            self.gt_boxes = torch.zeros((int(batch_size), self.max_gt, int(gt_columns)), dtype=torch.float32, device=device)
+        super().__init__(model, batch_size, max_points, level_factors=level_factors, warmup=warmup)
+
+    def _forward(self):
+        """The eager static path: what the graph holds.  Returns CenterPoint.post_processing_static's dict plus the
+        live row counts GraphedDetector.overflowed reads."""
+        bd = {'points': self.points, 'batch_size': self.batch_size, 'static_caps': self.static_caps}
+        if self.gt_boxes is not None:
+            bd['gt_boxes'] = self.gt_boxes
+        with torch.no_grad():
+            for m in self.modules:
+                bd = m(bd)
+            out = dict(self.model.post_processing_static(bd))
+        ms = bd['multi_scale_3d_features']
+        out['batch_size'] = self.batch_size
+        out['counts'] = {'voxels': bd['voxel_num_valid'], 'spconv2': ms['x_conv2'].n_valid,
+                         'spconv3': ms['x_conv3'].n_valid, 'spconv4': ms['x_conv4'].n_valid,
+                         'spconv_down2': bd['encoded_spconv_tensor'].n_valid}
+        return out
+
+    def __call__(self, points, gt_boxes=None):
+        """Copies the batch in and replays.  Returns the static output dict (overwritten by the next call)."""
+        if (gt_boxes is not None) != (self.gt_boxes is not None):
+            raise ValueError("gt_boxes go with a runner built with max_gt > 0, and only with one")
+        if gt_boxes is not None:
+            if gt_boxes.shape[0] != self.batch_size or gt_boxes.shape[1] > self.max_gt \
+                    or gt_boxes.shape[2] != self.gt_boxes.shape[2]:
+                raise ValueError("gt_boxes %s do not fit the captured buffer %s"
+                                 % (tuple(gt_boxes.shape), tuple(self.gt_boxes.shape)))
+            self.gt_boxes.zero_()
+            self.gt_boxes[:, :gt_boxes.shape[1]].copy_(gt_boxes, non_blocking=True)
+        return super().__call__(points)
+
+    def pred_dicts(self):
+        """The last call's result as model(batch) returns it in eval: (pred_dicts, recall_dict).  One host read."""
+        return self.model.pred_dicts_from_static(self.out)
+
+    def post_process(self):
+        return self.pred_dicts()
+
+
 class GraphedPointDetector(object):
     """Eval forward of a point detector (Point3DSSD: VoxelPointNet2FSMSGDistillation backbone, vote head) with its
     post-processing as ONE hipGraph replay.

@@ -168,6 +168,10 @@ SIGNATURES = {
     "spx_center_assign_targets": (_int, [_vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_int32,
                                          _i32p, _f32p, _f32p, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _i64,
                                          ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_center_decode_ws_bytes": (_sz, [ctypes.c_int32] * 5),
+    "spx_center_decode": (_int, [_vp] * 6 + [ctypes.c_int32] * 5 + [ctypes.c_float, _f32p, _f32p, _f32p, ctypes.c_float,
+                                                                   _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                                   _vp]),
 }
 
 _lib = None

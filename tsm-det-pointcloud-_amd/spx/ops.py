@@ -1689,3 +1689,54 @@ def center_assign_targets(gt_boxes, class_to_head_slot, head_channels, point_clo
         off += c
     return {"heatmaps": heatmaps, "target_boxes": list(boxes.unbind(0)), "inds": list(inds.unbind(0)),
             "masks": list(masks.unbind(0))}
+
+
+# ------------------------------------------------------------------------------------ centre-head box decoding (§21)
+
+CENTER_DECODE_MAX_K = 1024   # rows per frame spx_center_decode selects
+
+
+def center_decode(hm, center, center_z, dim, rot, vel, K, feature_map_stride, voxel_size, point_cloud_range,
+                  post_center_limit_range, score_thresh=None, raw=True):
+    """spx_center_decode: the K best cells of one head's heatmap for every frame, decoded to boxes, at static capacity
+    and with no host read.  hm (B, C, H, W), center (B, 2, H, W), center_z (B, 1, H, W), dim (B, 3, H, W), rot
+    (B, 2, H, W) (cos, sin), vel (B, 2, H, W) or None, fp32 on the GPU; raw: hm holds logits and dim logs (the head's
+    outputs), otherwise both are used as given (decode_bbox_from_heatmap's arguments).  Selection is by the value of hm
+    as given, descending, equal values lower flat index first.  Returns a dict: boxes (B, K, 7 | 9), scores (B, K),
+    labels (B, K) int32 (0-based channel), cells (B, K) int64, keep (B, K) uint8 (inside post_center_limit_range and,
+    with score_thresh, score > score_thresh), count (B) int32.  Rows that are not kept hold their decoded values."""
+    _need_gpu(hm, center, center_z, dim, rot, vel)
+    lib = _lib.load()
+    if hm.dim() != 4:
+        raise _lib.SpxError("center_decode: hm %s is not (B, C, H, W)" % (tuple(hm.shape),))
+    b, c, h, w = hm.shape
+    for name, t, ch in (("center", center, 2), ("center_z", center_z, 1), ("dim", dim, 3), ("rot", rot, 2),
+                        ("vel", vel, 2)):
+        if t is not None and (tuple(t.shape) != (b, ch, h, w) or t.device != hm.device):
+            raise _lib.SpxError("center_decode: %s %s on %s is not %s on %s"
+                                % (name, tuple(t.shape), t.device, (b, ch, h, w), hm.device))
+    k = int(K)
+    if not 1 <= k <= h * w:
+        raise _lib.SpxError("center_decode: K = %d is outside 1 .. H * W = %d" % (k, h * w))
+    hm, center, center_z, dim, rot = _f32(hm), _f32(center), _f32(center_z), _f32(dim), _f32(rot)
+    vel = None if vel is None else _f32(vel)
+    dev = hm.device
+    out = {"boxes": torch.empty((b, k, 7 if vel is None else 9), dtype=torch.float32, device=dev),
+           "scores": torch.empty((b, k), dtype=torch.float32, device=dev),
+           "labels": torch.empty((b, k), dtype=torch.int32, device=dev),
+           "cells": torch.empty((b, k), dtype=torch.int64, device=dev),
+           "keep": torch.empty((b, k), dtype=torch.uint8, device=dev),
+           "count": torch.empty((b,), dtype=torch.int32, device=dev)}
+    if b == 0:
+        return out
+    wsb = lib.spx_center_decode_ws_bytes(b, c, h, w, k)
+    ws = workspace(dev, wsb)
+    check(lib.spx_center_decode(_ptr(hm), _ptr(center), _ptr(center_z), _ptr(dim), _ptr(rot), _ptr(vel), b, c, h, w, k,
+                                float(feature_map_stride), f_arr([voxel_size[0], voxel_size[1]]),
+                                f_arr([point_cloud_range[0], point_cloud_range[1]]),
+                                f_arr([float(v) for v in post_center_limit_range]),
+                                0.0 if score_thresh is None else float(score_thresh), int(score_thresh is not None),
+                                int(bool(raw)), _ptr(out["boxes"]), _ptr(out["scores"]), _ptr(out["labels"]),
+                                _ptr(out["cells"]), _ptr(out["keep"]), _ptr(out["count"]), _ptr(ws), wsb, _stream(hm)),
+          "spx_center_decode")
+    return out
