@@ -944,6 +944,46 @@ int spx_center_decode(const float *hm, const float *center, const float *center_
                       float score_thresh, int has_score_thresh, int raw, float *boxes, float *scores, int32_t *labels,
                       int64_t *cells, uint8_t *keep, int32_t *count, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 22. Centre-head losses, forward + gradient, without a host read (csrc/center_loss.hip)
+ *    replaces, for one head and the whole batch: CenterHead.get_loss's sigmoid / clamp / neg_loss_cornernet, the cat
+ *      of the regression maps, _transpose_and_gather_feat and _reg_loss with the code and loss weights, and their
+ *      autograd (reference pcdet/utils/loss_utils.py:420-542, pcdet/models/dense_heads/center_head.py:221-251): some
+ *      fifty launches forward and as many backward, the gather's backward an index-add with float atomics.
+ *    Three launches per call (positive count + zero-fill of the regression gradients; the focal stream and the
+ *    regression slots with one double partial per block; a fixed-order sum of the partials).  No float atomics: the
+ *    outputs are bitwise reproducible.  The normalisers are counted on the device BEFORE the gradients are stored, so
+ *    the stored gradients are final; a batch without positives or without live slots takes the same path.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Inputs, device fp32 unless noted: hm [b, c, h, w] heatmap LOGITS; heatmap [b, c, h, w] the target, values in [0, 1],
+ *   1 exactly at the live centres; regs: HOST array of n_regs device pointers, map i [b, reg_channels[i], h, w]
+ *   (reg_channels: HOST int32[n_regs]), in HEAD_ORDER; D = sum of reg_channels; n_regs <= 5, D <= 10 and k <= 2048, else
+ *   SPX_ERR_UNSUPPORTED.  target_boxes [b, k, D], inds [b, k] int64 (y w + x), masks [b, k] int64 (1 live, 0 dead); all
+ *   three may be NULL when k == 0.  code_weights: HOST float[D].
+ * Focal term: p = clamp(sigmoid(x), 1e-4, 1 - 1e-4); a cell with heatmap == 1 adds log(p) (1 - p)^2, every other cell
+ *   log(1 - p) p^2 (1 - heatmap)^4; num_pos = #(heatmap == 1) over the batch; hm_loss = -(sum) / max(num_pos, 1) (with
+ *   num_pos == 0 the positive sum is empty: the reference's -neg_loss branch, selected on the device).
+ *   d_hm = d(hm_loss * cls_weight) / d(hm): exactly 0 where sigmoid(x) lies outside the clamp, passing AT a bound.
+ * Regression term: per live slot and column |regs[b, d, inds[b, k]] - target_boxes[b, k, d]|, summed per column and
+ *   divided by num = max(#(masks == 1) over the batch, 1).  d_regs = d(loc_loss * loc_weight) / d(regs): sign(pred -
+ *   target) * code_weights[d] * loc_weight / num at the live cells, sign(0) = 0, exact zeros everywhere else.  Several
+ *   live slots of a frame on one cell: the lowest slot writes the sum of their contributions, added in slot order.
+ *   A dead slot is never dereferenced: its inds and target_boxes influence nothing.  A live slot whose index lies
+ *   outside [0, h w) is skipped (it still counts in num).  A NaN target in a live slot makes its column of reg_loss (and
+ *   losses[1]) NaN; the gradient of that element is unspecified.
+ * Outputs, EVERY element written by the call's own launches: losses [2] = (hm_loss * cls_weight, sum_d(reg_loss[d] *
+ *   code_weights[d]) * loc_weight); reg_loss [D], unweighted; d_hm [b, c, h, w]; d_regs: HOST array of n_regs device
+ *   pointers, shaped like regs.  b == 0: SPX_OK, nothing launched, nothing written.  k == 0: the regression outputs are
+ *   zeros.  Any map with 2^31 or more elements: SPX_ERR_TOO_LARGE.
+ * ws: spx_center_head_loss_ws_bytes bytes. */
+size_t spx_center_head_loss_ws_bytes(int32_t b, int32_t c, int32_t h, int32_t w, int64_t k);
+int spx_center_head_loss(const float *hm, const float *heatmap, const float *const *regs, const int32_t *reg_channels,
+                         int32_t n_regs, const float *target_boxes, const int64_t *inds, const int64_t *masks, int32_t b,
+                         int32_t c, int32_t h, int32_t w, int64_t k, const float *code_weights, float cls_weight,
+                         float loc_weight, float *losses, float *reg_loss, float *d_hm, float *const *d_regs, void *ws,
+                         size_t ws_bytes, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

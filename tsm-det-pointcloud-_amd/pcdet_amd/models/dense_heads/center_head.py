@@ -20,7 +20,10 @@ What differs, on purpose:
   * Opt-in (POST_PROCESSING.FUSED: True, or static mode: `static_caps` in the batch dict): the boxes come from
     generate_predicted_boxes_static — spx.ops.center_decode (csrc/center_decode.hip) and spx.ops.point_post_process per
     head, static capacity, no host read — instead of the reference's sigmoid / exp / two topk / six gathers and its
-    per-frame mask, NMS and cat.  Without the key the reference's eager composition runs, unchanged."""
+    per-frame mask, NMS and cat.  Without the key the reference's eager composition runs, unchanged.
+  * Opt-in (LOSS_CONFIG.FUSED: True): get_loss dispatches to get_loss_fused — spx.ops.center_head_loss
+    (csrc/center_loss.hip) per head, losses and gradients in three launches, deterministic.  Without the key the torch
+    composition runs, unchanged."""
 import copy
 
 import numpy as np
@@ -136,6 +139,8 @@ class CenterHead(nn.Module):
         return torch.clamp(x.sigmoid(), min=1e-4, max=1 - 1e-4)
 
     def get_loss(self):
+        if self.model_cfg.LOSS_CONFIG.get('FUSED', False):      # opt-in: spx.ops.center_head_loss per head
+            return self.get_loss_fused()
         pred_dicts = self.forward_ret_dict['pred_dicts']
         target_dicts = self.forward_ret_dict['target_dicts']
         weights = self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
@@ -151,6 +156,37 @@ class CenterHead(nn.Module):
             loc_loss = (reg_loss * self.code_weights.to(reg_loss.dtype)).sum()
             loc_loss = loc_loss * weights['loc_weight']
 
+            loss = loss + hm_loss + loc_loss
+            tb_dict['hm_loss_head_%d' % idx] = hm_loss.detach()
+            tb_dict['loc_loss_head_%d' % idx] = loc_loss.detach()
+        tb_dict['rpn_loss'] = loss.detach()
+        return loss, tb_dict
+
+    def get_loss_fused(self):
+        """get_loss with each head's two losses and their gradients from spx.ops.center_head_loss (csrc/center_loss.hip):
+        three launches per head forward, one multiplication per head output backward, no host read, no float atomics, so
+        the gradients are bitwise reproducible also where two boxes share a cell.  Same return value as get_loss: (loss,
+        tb_dict) with the same keys and 0-d tensors.  The regression maps are passed one by one in HEAD_ORDER, not
+        concatenated.  A slot with mask 0 is never read (see the op's docstring)."""
+        pred_dicts = self.forward_ret_dict['pred_dicts']
+        target_dicts = self.forward_ret_dict['target_dicts']
+        weights = self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
+        if len(target_dicts.get('heatmap_masks', [])) > 0:
+            raise NotImplementedError('get_loss_fused: a focal mask (heatmap_masks) is not supported; '
+                                      'set LOSS_CONFIG.FUSED False')
+        order = list(self.separate_head_cfg.HEAD_ORDER)
+        code_weights = [float(v) for v in weights['code_weights']]
+        num_cols = sum(int(self.separate_head_cfg.HEAD_DICT[name]['out_channels']) for name in order)
+        if num_cols not in (8, 10) or len(code_weights) != num_cols:
+            raise NotImplementedError('get_loss_fused: HEAD_ORDER %s has %d regression columns and %d code_weights '
+                                      '(8, or 10 with vel, only)' % (order, num_cols, len(code_weights)))
+        tb_dict = {}
+        loss = 0
+        for idx, pred_dict in enumerate(pred_dicts):
+            hm_loss, loc_loss = loss_utils._FusedCenterHeadLoss.apply(
+                target_dicts['heatmaps'][idx], target_dicts['target_boxes'][idx], target_dicts['inds'][idx],
+                target_dicts['masks'][idx], code_weights, float(weights['cls_weight']), float(weights['loc_weight']),
+                pred_dict['hm'], *[pred_dict[name] for name in order])
             loss = loss + hm_loss + loc_loss
             tb_dict['hm_loss_head_%d' % idx] = hm_loss.detach()
             tb_dict['loc_loss_head_%d' % idx] = loc_loss.detach()

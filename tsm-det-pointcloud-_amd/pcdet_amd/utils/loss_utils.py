@@ -88,6 +88,29 @@ class _FusedPointSegLoss(torch.autograd.Function):
         return (d_scores * g).view(ctx.shape), None, None, None, None
 
 
+class _FusedCenterHeadLoss(torch.autograd.Function):
+    """One centre head's two 0-d losses (hm_loss * cls_weight, loc_loss * loc_weight) with their gradients w.r.t. the
+    heatmap logits and the regression maps from one libspx launch group (csrc/center_loss.hip, no host read, no float
+    atomics); backward scales the saved gradients.  The normalisers are applied inside the op (count first), so the
+    saved gradients are final.  apply(heatmap, target_boxes, inds, masks, code_weights, cls_weight, loc_weight, hm,
+    *regs) -> (hm_loss, loc_loss); code_weights: host floats."""
+
+    @staticmethod
+    def forward(ctx, heatmap, target_boxes, inds, masks, code_weights, cls_weight, loc_weight, hm, *regs):
+        from spx import ops
+        losses, _reg_loss, d_hm, d_regs = ops.center_head_loss(hm, heatmap, regs, target_boxes, inds, masks,
+                                                               code_weights, cls_weight, loc_weight)
+        ctx.save_for_backward(d_hm, *d_regs)
+        ctx.dtypes = [hm.dtype] + [t.dtype for t in regs]
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_hm, g_loc):
+        d_hm, *d_regs = ctx.saved_tensors
+        grads = [(d_hm * g_hm).to(ctx.dtypes[0])] + [(d * g_loc).to(t) for d, t in zip(d_regs, ctx.dtypes[1:])]
+        return (None,) * 7 + tuple(grads)
+
+
 class PointSASALoss(nn.Module):
     """The reference's layer-wise SASA segmentation loss (loss_utils.py:545-704) up to its targets: the constructor
     (no parameters or buffers), assign_target and forward, which assigns the targets of every weighted layer, one HIP

@@ -22,6 +22,7 @@ _int = ctypes.c_int
 _sz = ctypes.c_size_t
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _f32p = ctypes.POINTER(ctypes.c_float)
+_vpp = ctypes.POINTER(ctypes.c_void_p)   # host array of device pointers
 
 #: name -> (restype, argtypes).  Mirrors include/spx.h one to one (tests/test_abi.py checks the header).
 class PointMlp(ctypes.Structure):
@@ -172,6 +173,9 @@ SIGNATURES = {
     "spx_center_decode": (_int, [_vp] * 6 + [ctypes.c_int32] * 5 + [ctypes.c_float, _f32p, _f32p, _f32p, ctypes.c_float,
                                                                    _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                                                    _vp]),
+    "spx_center_head_loss_ws_bytes": (_sz, [ctypes.c_int32] * 4 + [_i64]),
+    "spx_center_head_loss": (_int, [_vp, _vp, _vpp, _i32p, ctypes.c_int32, _vp, _vp, _vp] + [ctypes.c_int32] * 4 +
+                             [_i64, _f32p, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vpp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1740,3 +1740,81 @@ def center_decode(hm, center, center_z, dim, rot, vel, K, feature_map_stride, vo
                                 _ptr(out["cells"]), _ptr(out["keep"]), _ptr(out["count"]), _ptr(ws), wsb, _stream(hm)),
           "spx_center_decode")
     return out
+
+
+# -------------------------------------------------------------------------------------------- centre-head losses (§22)
+
+def center_head_loss(hm, heatmap, regs, target_boxes, inds, masks, code_weights, cls_weight, loc_weight):
+    """spx_center_head_loss: one centre head's focal and L1 losses with their gradients for the whole batch, three
+    launches, no host read, no float atomics (bitwise reproducible).  hm (B, C, H, W) heatmap logits and heatmap
+    (B, C, H, W) the target of center_assign_targets (1 exactly at the live centres), fp32 on the GPU; regs: the four or
+    five regression maps (B, d_i, H, W) in HEAD_ORDER (not concatenated), D = sum d_i <= 10; target_boxes (B, K, D),
+    inds and masks (B, K) int64; code_weights: D HOST floats (a sequence or a CPU tensor, so that nothing is read back).
+    Returns (losses fp32[2] = (hm_loss * cls_weight, (reg_loss * code_weights).sum() * loc_weight), reg_loss fp32[D]
+    unweighted, d_hm like hm, d_regs: one tensor like each of regs), the gradients being those of the two weighted
+    losses, every element written by the op (zeros off the live cells).
+
+    Semantics are CenterHead.get_loss's (clamped sigmoid, neg_loss_cornernet with mask=None and its device-side
+    num_pos == 0 branch, _reg_loss), except that a slot with masks == 0 is never dereferenced: its inds and target_boxes
+    influence nothing.  center_assign_targets zero-fills dead slots, so this differs from the composition only for a NaN
+    in a dead slot's target (there NaN * 0 poisons the composition's column), which the target op never produces.  A
+    NaN target in a LIVE slot makes its column of reg_loss NaN, as in the composition.  Where sigmoid(hm) lies outside
+    [1e-4, 1 - 1e-4] d_hm is exactly 0.  B == 0 launches nothing and returns zeros; with K == 0 the regression part
+    launches nothing of its own and its outputs are zeros."""
+    regs = list(regs)
+    _need_gpu(hm, heatmap, target_boxes, inds, masks, *regs)
+    lib = _lib.load()
+    if hm.dim() != 4 or not hm.is_floating_point():
+        raise _lib.SpxError("center_head_loss: hm %s %s is not float (B, C, H, W)" % (tuple(hm.shape), hm.dtype))
+    b, c, h, w = hm.shape
+    dev = hm.device
+    if tuple(heatmap.shape) != (b, c, h, w) or not heatmap.is_floating_point() or heatmap.device != dev:
+        raise _lib.SpxError("center_head_loss: heatmap %s %s on %s is not float %s on %s"
+                            % (tuple(heatmap.shape), heatmap.dtype, heatmap.device, (b, c, h, w), dev))
+    if not 1 <= len(regs) <= 5:
+        raise _lib.SpxError("center_head_loss: %d regression maps, expected 1 .. 5" % len(regs))
+    for i, t in enumerate(regs):
+        if t.dim() != 4 or t.shape[0] != b or t.shape[1] < 1 or tuple(t.shape[2:]) != (h, w) \
+                or not t.is_floating_point() or t.device != dev:
+            raise _lib.SpxError("center_head_loss: regs[%d] %s %s on %s is not float (%d, d, %d, %d) on %s"
+                                % (i, tuple(t.shape), t.dtype, t.device, b, h, w, dev))
+    chans = [int(t.shape[1]) for t in regs]
+    d = sum(chans)
+    if target_boxes.dim() != 3 or target_boxes.shape[0] != b or target_boxes.shape[2] != d \
+            or not target_boxes.is_floating_point() or target_boxes.device != dev:
+        raise _lib.SpxError("center_head_loss: target_boxes %s %s is not float (%d, K, %d): the regression maps have %s "
+                            "channels" % (tuple(target_boxes.shape), target_boxes.dtype, b, d, chans))
+    k = target_boxes.shape[1]
+    for name, t in (("inds", inds), ("masks", masks)):
+        if tuple(t.shape) != (b, k) or t.dtype != torch.int64 or t.device != dev:
+            raise _lib.SpxError("center_head_loss: %s %s %s on %s is not int64 (%d, %d) on %s"
+                                % (name, tuple(t.shape), t.dtype, t.device, b, k, dev))
+    if isinstance(code_weights, torch.Tensor):
+        if code_weights.is_cuda:
+            raise _lib.SpxError("center_head_loss: code_weights is a GPU tensor; pass host floats (reading it back would "
+                                "be a host sync)")
+        code_weights = code_weights.tolist()
+    code_weights = [float(v) for v in code_weights]
+    if len(code_weights) != d:
+        raise _lib.SpxError("center_head_loss: %d code_weights for %d regression columns" % (len(code_weights), d))
+    hm, heatmap, target_boxes = _f32(hm), _f32(heatmap), _f32(target_boxes)
+    regs = [_f32(t) for t in regs]
+    inds, masks = inds.detach().contiguous(), masks.detach().contiguous()
+    losses = torch.empty((2,), dtype=torch.float32, device=dev)
+    reg_loss = torch.empty((d,), dtype=torch.float32, device=dev)
+    d_hm = torch.empty_like(hm)
+    d_regs = [torch.empty_like(t) for t in regs]
+    if b == 0:
+        losses.zero_()
+        reg_loss.zero_()
+        return losses, reg_loss, d_hm, d_regs
+    n = len(regs)
+    wsb = lib.spx_center_head_loss_ws_bytes(b, c, h, w, k)
+    ws = workspace(dev, wsb)
+    check(lib.spx_center_head_loss(_ptr(hm), _ptr(heatmap), (ctypes.c_void_p * n)(*[t.data_ptr() for t in regs]),
+                                   (ctypes.c_int32 * n)(*chans), n, _ptr(target_boxes) if k > 0 else None,
+                                   _ptr(inds) if k > 0 else None, _ptr(masks) if k > 0 else None, b, c, h, w, k,
+                                   f_arr(code_weights), float(cls_weight), float(loc_weight), _ptr(losses),
+                                   _ptr(reg_loss), _ptr(d_hm), (ctypes.c_void_p * n)(*[t.data_ptr() for t in d_regs]),
+                                   _ptr(ws), wsb, _stream(hm)), "spx_center_head_loss")
+    return losses, reg_loss, d_hm, d_regs
