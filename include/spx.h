@@ -984,6 +984,59 @@ int spx_center_head_loss(const float *hm, const float *heatmap, const float *con
                          float loc_weight, float *losses, float *reg_loss, float *d_hm, float *const *d_regs, void *ws,
                          size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 23. PillarVFE with one last-layer PFNLayer, forward + parameter gradients (csrc/pillar_vfe.hip)
+ *    replaces: PillarVFE.forward + PFNLayer.forward for NUM_FILTERS of length 1 with USE_NORM (reference
+ *      pcdet/models/backbones_3d/vfe/pillar_vfe.py:29-123): the feature cat, the mask multiply, Linear(C_in, 64,
+ *      bias=False), BatchNorm1d between two permutes, ReLU and the max over the T rows of a pillar, each a pass over
+ *      an [M, T, 64] tensor, and their autograd.
+ *    Training forward 3 launches (S1 = sum f and G = sum f f^T over the real points, one double partial per block; the
+ *    fixed-order sum, the batch statistics from S1, G and the weight, the running statistics; the per-pillar max), eval
+ *    forward 1, backward 2.  No float atomics, every sum in double in a fixed order: outputs and gradients are bitwise
+ *    reproducible.  No host read: every launch shape depends on host values only.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Inputs, device: voxels [m, t, c] fp32 (x, y, z first), 1 <= t <= 32, 3 <= c <= 6; num_points [m] int32; coords
+ *   [m, 4] int32 (b, z, y, x); d_n: device int64[1] live row count (clamped to m) or NULL = m; weight [c_out, c_in]
+ *   fp32, c_in = (use_absolute_xyz ? c + 6 : c + 3) + (with_distance ? 1 : 0) else SPX_ERR_INVALID_ARG; c_out != 64:
+ *   SPX_ERR_UNSUPPORTED; gamma, beta, running_mean, running_var [c_out] fp32, num_batches_tracked int64[1] (the three
+ *   may be NULL in training: no running statistics are kept); geom6: HOST float[6] = voxel size (x, y, z), then the
+ *   centre offsets voxel / 2 + range_lo (x, y, z).
+ * Features of point t < n = min(max(num_points, 0), t) of a pillar, in weight-column order: [x, y, z if
+ *   use_absolute_xyz | columns 3 .. c - 1 | xyz - (sum of xyz over the n real points) / n | xyz - centre | |xyz| if
+ *   with_distance], centre = fl32(fl32(coord * voxel) + offset); differences, sums and products are taken in double.
+ *   Rows t >= n are all-zero feature rows: their linear output is 0, they count in the statistics (sample count N =
+ *   live rows * t) and their value relu(beta - mean * gamma * invstd) takes part in the max of a pillar with n < t.
+ *   A live row with num_points <= 0 is all padding (the reference divides by 0 there).
+ * training != 0: z = (x - mean) * invstd * gamma + beta with the biased batch variance, invstd = 1 / sqrt(var + eps);
+ *   running_mean / running_var move by `momentum` towards the batch mean / UNBIASED variance, num_batches_tracked
+ *   += 1; save_mean, save_invstd [c_out] fp32 and stats [spx_pillar_vfe_stats_len()] doubles (G, S1, mean, invstd, N:
+ *   what the backward needs) are written.  training == 0: z from the running statistics; save_*, stats, ws unused.
+ * Outputs: out [m, c_out] = max over the t rows of relu(z); arg [m, c_out] uint8 = the winning row's index, t when a
+ *   padding row won; equal values take the lowest index (so a pillar whose values are all 0 reports its first row).
+ *   Rows >= the live count are never read; their out and arg are exact zeros.  m == 0: SPX_OK, nothing launched.
+ * ws: spx_pillar_vfe_ws_bytes(m) bytes (both entry points). */
+size_t spx_pillar_vfe_stats_len(void);
+size_t spx_pillar_vfe_ws_bytes(int64_t m);
+int spx_pillar_vfe_fwd(const float *voxels, const int32_t *num_points, const int32_t *coords, int64_t m, const int64_t *d_n,
+                       int32_t t, int32_t c, const float *weight, int32_t c_in, int32_t c_out, const float *gamma,
+                       const float *beta, float *running_mean, float *running_var, int64_t *num_batches_tracked,
+                       float momentum, float eps, const float *geom6, int use_absolute_xyz, int with_distance,
+                       int training, float *out, uint8_t *arg, float *save_mean, float *save_invstd, double *stats,
+                       void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* d_weight [c_out, c_in], d_gamma, d_beta [c_out] from d_out [m, c_out], every element written.  g = d_out at the row
+ *   arg selects of each live (pillar, channel) with out > 0, 0 on every other of the N rows.  training != 0 (stats of
+ *   the forward): the exact train-mode BatchNorm gradient, d_beta = sum g, d_gamma = sum g xhat, d_weight = gamma
+ *   invstd [sum g f - (d_beta / N) S1 - (d_gamma / N) invstd (G w - mean S1)], without an [m, t, c_out] tensor.
+ *   training == 0 (running statistics): d_weight = gamma invstd sum g f.  No gradient w.r.t. voxels exists. */
+int spx_pillar_vfe_bwd(const float *voxels, const int32_t *num_points, const int32_t *coords, int64_t m, const int64_t *d_n,
+                       int32_t t, int32_t c, const float *weight, int32_t c_in, int32_t c_out, const float *gamma,
+                       const float *running_mean, const float *running_var, float eps, const float *geom6,
+                       int use_absolute_xyz, int with_distance, int training, const float *out, const uint8_t *arg,
+                       const float *d_out, const double *stats, float *d_weight, float *d_gamma, float *d_beta, void *ws,
+                       size_t ws_bytes, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

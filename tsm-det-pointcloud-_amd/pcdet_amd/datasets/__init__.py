@@ -22,6 +22,15 @@ class SyntheticDataset(Dataset):
         self.point_cloud_range = np.array(geom['point_cloud_range'], dtype=np.float32)
         self.voxel_size = list(geom['voxel_size'])
         self.grid_size = synthetic.grid_size_of(geom)          # (gx, gy, gz), data_processor.py:129-130
+        if dataset_cfg is not None and dataset_cfg.get('SYNTHETIC_GEOMETRY_FROM_CONFIG', False):
+            # a model yaml that overrides POINT_CLOUD_RANGE and the voxeliser's VOXEL_SIZE (pointpillar.yaml): the
+            # frames stay those of the synthetic configuration, the model's grid is the yaml's
+            self.point_cloud_range = np.array(dataset_cfg.POINT_CLOUD_RANGE, dtype=np.float32)
+            for proc in dataset_cfg.DATA_PROCESSOR:
+                if 'VOXEL_SIZE' in proc:
+                    self.voxel_size = [float(v) for v in proc['VOXEL_SIZE']]
+            self.grid_size = synthetic.grid_size_of(dict(point_cloud_range=self.point_cloud_range.tolist(),
+                                                         voxel_size=self.voxel_size))
         self.point_feature_encoder = SimpleNamespace(num_point_features=geom['num_point_features'])
         self.depth_downsample_factor = None
         self.max_points_per_voxel = geom['max_points_per_voxel']

@@ -1,9 +1,11 @@
 from .dynamic_mean_vfe import DynamicMeanVFE
 from .mean_vfe import MeanVFE
+from .pillar_vfe import PillarVFE
 from .vfe_template import VFETemplate
 
 __all__ = {
     'VFETemplate': VFETemplate,
     'MeanVFE': MeanVFE,
     'DynamicMeanVFE': DynamicMeanVFE,
+    'PillarVFE': PillarVFE,
 }

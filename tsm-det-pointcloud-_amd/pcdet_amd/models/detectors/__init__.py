@@ -1,6 +1,7 @@
 from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .point_3dssd import Point3DSSD
+from .pointpillar import PointPillar
 from .second_net import SECONDNet
 
 __all__ = {
@@ -8,6 +9,7 @@ __all__ = {
     'SECONDNet': SECONDNet,
     '3DSSD': Point3DSSD,
     'CenterPoint': CenterPoint,
+    'PointPillar': PointPillar,
 }
 
 

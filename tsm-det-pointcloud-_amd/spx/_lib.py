@@ -176,6 +176,14 @@ SIGNATURES = {
     "spx_center_head_loss_ws_bytes": (_sz, [ctypes.c_int32] * 4 + [_i64]),
     "spx_center_head_loss": (_int, [_vp, _vp, _vpp, _i32p, ctypes.c_int32, _vp, _vp, _vp] + [ctypes.c_int32] * 4 +
                              [_i64, _f32p, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vpp, _vp, _sz, _vp]),
+    "spx_pillar_vfe_stats_len": (_sz, []),
+    "spx_pillar_vfe_ws_bytes": (_sz, [_i64]),
+    "spx_pillar_vfe_fwd": (_int, [_vp, _vp, _vp, _i64, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32,
+                                  ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _f32p, _int, _int,
+                                  _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_pillar_vfe_bwd": (_int, [_vp, _vp, _vp, _i64, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32,
+                                  ctypes.c_int32, _vp, _vp, _vp, ctypes.c_float, _f32p, _int, _int, _int, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

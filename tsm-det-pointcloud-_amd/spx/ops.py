@@ -1818,3 +1818,189 @@ def center_head_loss(hm, heatmap, regs, target_boxes, inds, masks, code_weights,
                                    _ptr(reg_loss), _ptr(d_hm), (ctypes.c_void_p * n)(*[t.data_ptr() for t in d_regs]),
                                    _ptr(ws), wsb, _stream(hm)), "spx_center_head_loss")
     return losses, reg_loss, d_hm, d_regs
+
+
+# --------------------------------------------------------------------------------- PillarVFE, one last-layer PFN (§23)
+
+PILLAR_VFE_MAX_T = 32     # points per pillar spx_pillar_vfe_* takes
+PILLAR_VFE_C_OUT = 64     # the one output width it is instantiated for
+
+
+def pillar_vfe_c_in(c, use_absolute_xyz, with_distance):
+    """Width of PillarVFE's per-point feature vector for c raw columns."""
+    return (c + 6 if use_absolute_xyz else c + 3) + (1 if with_distance else 0)
+
+
+def _pillar_geom(voxel_size, offsets):
+    return f_arr([float(v) for v in voxel_size] + [float(v) for v in offsets])
+
+
+def _pillar_inputs(what, voxels, num_points, coords, weight, use_absolute_xyz, with_distance, d_n):
+    """Shape, dtype and device checks shared by the two entry points -> contiguous inputs."""
+    if voxels.dim() != 3 or voxels.dtype != torch.float32:
+        raise _lib.SpxError("%s: voxels %s %s is not float32 (M, T, C)" % (what, tuple(voxels.shape), voxels.dtype))
+    m, t, c = voxels.shape
+    dev = voxels.device
+    if not 1 <= t <= PILLAR_VFE_MAX_T or not 3 <= c <= 6:
+        raise _lib.SpxError("%s: T = %d, C = %d outside 1 <= T <= %d, 3 <= C <= 6" % (what, t, c, PILLAR_VFE_MAX_T))
+    if tuple(num_points.shape) != (m,) or num_points.device != dev or num_points.dtype not in (torch.int32, torch.int64):
+        raise _lib.SpxError("%s: num_points %s %s on %s is not an integer (%d,) on %s"
+                            % (what, tuple(num_points.shape), num_points.dtype, num_points.device, m, dev))
+    if tuple(coords.shape) != (m, 4) or coords.device != dev or coords.dtype not in (torch.int32, torch.int64):
+        raise _lib.SpxError("%s: coords %s %s on %s is not an integer (%d, 4) on %s"
+                            % (what, tuple(coords.shape), coords.dtype, coords.device, m, dev))
+    c_in = pillar_vfe_c_in(c, use_absolute_xyz, with_distance)
+    if weight.dim() != 2 or weight.shape[1] != c_in or weight.dtype != torch.float32 or weight.device != dev:
+        raise _lib.SpxError("%s: weight %s %s is not float32 (C_out, %d) on %s: C = %d, use_absolute_xyz = %s, "
+                            "with_distance = %s" % (what, tuple(weight.shape), weight.dtype, c_in, dev, c,
+                                                    bool(use_absolute_xyz), bool(with_distance)))
+    if weight.shape[0] != PILLAR_VFE_C_OUT:
+        raise _lib.SpxError("%s: C_out = %d is not supported, the kernels are built for C_out = %d"
+                            % (what, weight.shape[0], PILLAR_VFE_C_OUT))
+    if d_n is not None and isinstance(d_n, torch.Tensor) and d_n.dtype == torch.int32 and d_n.numel() == 1:
+        d_n = d_n.to(torch.int64).view(1)              # a device cast, no host read
+    d_n = _d_n("%s: d_n" % what, d_n, dev)
+    return (voxels.contiguous(), num_points.to(torch.int32).contiguous(), coords.to(torch.int32).contiguous(),
+            weight.detach().contiguous(), d_n, m, t, c, c_in)
+
+
+def _vec64(what, name, v, dev, dtype=torch.float32, n=PILLAR_VFE_C_OUT):
+    if v is None:
+        return None
+    if tuple(v.shape) != (n,) or v.dtype != dtype or v.device != dev or not v.is_contiguous():
+        raise _lib.SpxError("%s: %s %s %s on %s is not a contiguous %s (%d,) on %s"
+                            % (what, name, tuple(v.shape), v.dtype, v.device, dtype, n, dev))
+    return v
+
+
+def pillar_vfe_fwd(voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, num_batches_tracked,
+                   momentum, eps, voxel_size, offsets, use_absolute_xyz=True, with_distance=False, training=False,
+                   d_n=None):
+    """spx_pillar_vfe_fwd (include/spx.h §23): PillarVFE with one last-layer PFNLayer, Linear + BatchNorm1d + ReLU + max
+    over the points of every pillar without the (M, T, C_out) tensor.  voxels (M, T, C) float32, num_points (M,),
+    coords (M, 4) (b, z, y, x), weight (64, C_in); voxel_size / offsets: 3 host floats each (x, y, z), offsets = voxel / 2
+    + range_lo; d_n: device int64[1] live row count (static capacity), rows at or beyond it are never read and come back
+    as zeros.  training: batch statistics, and running_mean / running_var / num_batches_tracked are updated IN PLACE.
+    Returns dict(out (M, 64), arg (M, 64) uint8: the winning point of each (pillar, channel), T = a padding row;
+    mean, invstd (64,) and stats (double, for pillar_vfe_bwd) in training, else None).  No host read."""
+    what = "pillar_vfe_fwd"
+    _need_gpu(voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, num_batches_tracked, d_n)
+    lib = _lib.load()
+    voxels, num, coords, weight, d_n, m, t, c, c_in = _pillar_inputs(what, voxels, num_points, coords, weight,
+                                                                      use_absolute_xyz, with_distance, d_n)
+    dev = voxels.device
+    gamma = _vec64(what, "gamma", gamma.detach(), dev)
+    beta = _vec64(what, "beta", beta.detach(), dev)
+    running_mean = _vec64(what, "running_mean", running_mean, dev)
+    running_var = _vec64(what, "running_var", running_var, dev)
+    nbt = None
+    if num_batches_tracked is not None:
+        nbt = _vec64(what, "num_batches_tracked", num_batches_tracked.view(-1), dev, torch.int64, 1)
+    if not training and (running_mean is None or running_var is None):
+        raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    out = torch.empty((m, PILLAR_VFE_C_OUT), dtype=torch.float32, device=dev)
+    arg = torch.empty((m, PILLAR_VFE_C_OUT), dtype=torch.uint8, device=dev)
+    mean = invstd = stats = None
+    if training:
+        mean = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+        invstd = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+        stats = torch.empty((int(lib.spx_pillar_vfe_stats_len()),), dtype=torch.float64, device=dev)
+    res = dict(out=out, arg=arg, mean=mean, invstd=invstd, stats=stats)
+    if m == 0:
+        if training:
+            raise _lib.SpxError("%s: training-mode batch statistics of 0 pillars" % what)
+        return res
+    wsb = lib.spx_pillar_vfe_ws_bytes(m)
+    ws = workspace(dev, wsb)
+    check(lib.spx_pillar_vfe_fwd(_ptr(voxels), _ptr(num), _ptr(coords), m, _ptr(d_n), t, c, _ptr(weight), c_in,
+                                 weight.shape[0], _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(nbt),
+                                 float(momentum), float(eps), _pillar_geom(voxel_size, offsets),
+                                 1 if use_absolute_xyz else 0, 1 if with_distance else 0, 1 if training else 0, _ptr(out),
+                                 _ptr(arg), _ptr(mean), _ptr(invstd), _ptr(stats), _ptr(ws), wsb, _stream(voxels)),
+          "spx_pillar_vfe_fwd")
+    return res
+
+
+def pillar_vfe_bwd(d_out, out, arg, stats, voxels, num_points, coords, weight, gamma, running_mean, running_var, eps,
+                   voxel_size, offsets, use_absolute_xyz=True, with_distance=False, training=True, d_n=None):
+    """spx_pillar_vfe_bwd: (d_weight (64, C_in), d_gamma (64,), d_beta (64,)) from d_out (M, 64) and what pillar_vfe_fwd
+    returned (out, arg, and stats in training): the exact train-mode BatchNorm gradient (eval: on the running statistics)
+    from the selected rows alone.  Deterministic, no host read."""
+    what = "pillar_vfe_bwd"
+    _need_gpu(d_out, out, arg, stats, voxels, num_points, coords, weight, gamma, running_mean, running_var, d_n)
+    lib = _lib.load()
+    voxels, num, coords, weight, d_n, m, t, c, c_in = _pillar_inputs(what, voxels, num_points, coords, weight,
+                                                                      use_absolute_xyz, with_distance, d_n)
+    dev = voxels.device
+    shape = (m, PILLAR_VFE_C_OUT)
+    if tuple(d_out.shape) != shape or d_out.device != dev or tuple(out.shape) != shape or out.dtype != torch.float32 \
+            or tuple(arg.shape) != shape or arg.dtype != torch.uint8:
+        raise _lib.SpxError("%s: d_out %s, out %s %s, arg %s %s do not match float32 / float32 / uint8 %s"
+                            % (what, tuple(d_out.shape), tuple(out.shape), out.dtype, tuple(arg.shape), arg.dtype, shape))
+    d_out, out, arg = _f32(d_out), out.contiguous(), arg.contiguous()
+    gamma = _vec64(what, "gamma", gamma.detach(), dev)
+    if training:
+        stats = _vec64(what, "stats", stats, dev, torch.float64, int(lib.spx_pillar_vfe_stats_len()))
+        if stats is None:
+            raise _lib.SpxError("%s: training mode needs the forward's stats" % what)
+    else:
+        running_mean = _vec64(what, "running_mean", running_mean, dev)
+        running_var = _vec64(what, "running_var", running_var, dev)
+        if running_mean is None or running_var is None:
+            raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    d_weight = torch.empty_like(weight)
+    d_gamma = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    d_beta = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    if m == 0:
+        return d_weight.zero_(), d_gamma.zero_(), d_beta.zero_()
+    wsb = lib.spx_pillar_vfe_ws_bytes(m)
+    ws = workspace(dev, wsb)
+    check(lib.spx_pillar_vfe_bwd(_ptr(voxels), _ptr(num), _ptr(coords), m, _ptr(d_n), t, c, _ptr(weight), c_in,
+                                 weight.shape[0], _ptr(gamma), _ptr(running_mean), _ptr(running_var), float(eps),
+                                 _pillar_geom(voxel_size, offsets), 1 if use_absolute_xyz else 0,
+                                 1 if with_distance else 0, 1 if training else 0, _ptr(out), _ptr(arg), _ptr(d_out),
+                                 _ptr(stats) if training else None, _ptr(d_weight), _ptr(d_gamma), _ptr(d_beta), _ptr(ws),
+                                 wsb, _stream(voxels)), "spx_pillar_vfe_bwd")
+    return d_weight, d_gamma, d_beta
+
+
+class _PillarVFEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, gamma, beta, voxels, num_points, coords, running_mean, running_var, nbt, cfg):
+        res = pillar_vfe_fwd(voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, nbt,
+                             cfg["momentum"], cfg["eps"], cfg["voxel_size"], cfg["offsets"], cfg["use_absolute_xyz"],
+                             cfg["with_distance"], cfg["training"], cfg["d_n"])
+        ctx.cfg = cfg
+        ctx.inputs = (voxels, num_points, coords, running_mean, running_var)
+        ctx.save_for_backward(weight, gamma, res["out"], res["arg"], *([res["stats"]] if cfg["training"] else []))
+        ctx.mark_non_differentiable(res["arg"])
+        mean, invstd = res["mean"], res["invstd"]
+        if mean is None:
+            mean = invstd = weight.new_empty((0,))
+        ctx.mark_non_differentiable(mean, invstd)
+        return res["out"], res["arg"], mean, invstd
+
+    @staticmethod
+    def backward(ctx, d_out, _d_arg, _d_mean, _d_invstd):
+        cfg = ctx.cfg
+        weight, gamma, out, arg = ctx.saved_tensors[:4]
+        stats = ctx.saved_tensors[4] if cfg["training"] else None
+        voxels, num_points, coords, running_mean, running_var = ctx.inputs
+        dw, dg, db = pillar_vfe_bwd(d_out, out, arg, stats, voxels, num_points, coords, weight, gamma, running_mean,
+                                    running_var, cfg["eps"], cfg["voxel_size"], cfg["offsets"], cfg["use_absolute_xyz"],
+                                    cfg["with_distance"], cfg["training"], cfg["d_n"])
+        return dw, dg, db, None, None, None, None, None, None, None
+
+
+def pillar_vfe(voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
+               eps, voxel_size, offsets, use_absolute_xyz=True, with_distance=False, training=False, d_n=None):
+    """The differentiable form of pillar_vfe_fwd / pillar_vfe_bwd: (pillar_features (M, 64), arg (M, 64) uint8, mean,
+    invstd) with gradients for weight, gamma and beta.  In eval mode the running statistics are read a second time by the
+    backward, so they must not change in between.  There is no gradient with respect to voxels."""
+    if voxels.requires_grad:
+        raise _lib.SpxError("pillar_vfe: voxels.requires_grad is set, but the op has no gradient with respect to voxels")
+    cfg = dict(momentum=float(momentum), eps=float(eps), voxel_size=[float(v) for v in voxel_size],
+               offsets=[float(v) for v in offsets], use_absolute_xyz=bool(use_absolute_xyz),
+               with_distance=bool(with_distance), training=bool(training), d_n=d_n)
+    return _PillarVFEFn.apply(weight, gamma, beta, voxels, num_points, coords, running_mean, running_var,
+                              num_batches_tracked, cfg)
