@@ -49,6 +49,9 @@ extern "C" {
 #define SPX_ERR_RING_STALL (-8)   /* DEVICE-side: a wave of spx_conv_gemm_ring gave up a (bounded) wait on the weight ring:
                                      the launch's output is incomplete; via d_status.  Never seen; the exit exists so that a
                                      protocol fault ends as an error code and not as a hung GPU                            */
+#define SPX_ERR_BATCH_STATS (-10) /* DEVICE-side: a training-mode forward of spx_dynamic_pillar_vfe_fwd met fewer than two
+                                     kept points (torch raises there); the running statistics and the counter were left
+                                     untouched                                                                           */
 #define SPX_ERR_OUT_OF_GRID (-9)  /* DEVICE-side: spx_voxel_table_build met a live row whose (batch, z, y, x) lies outside the
                                      table; the row was skipped; via d_status                                               */
 
@@ -1036,6 +1039,83 @@ int spx_pillar_vfe_bwd(const float *voxels, const int32_t *num_points, const int
                        int use_absolute_xyz, int with_distance, int training, const float *out, const uint8_t *arg,
                        const float *d_out, const double *stats, float *d_weight, float *d_gamma, float *d_beta, void *ws,
                        size_t ws_bytes, spx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 24. DynamicPillarVFE: sync-free pillarisation and one fused last-layer PFNLayerV2 (csrc/dyn_pillar_vfe.hip)
+ *    replaces: DynamicPillarVFE.forward + PFNLayerV2.forward for NUM_FILTERS of length 1 with USE_NORM (reference
+ *      pcdet/models/backbones_3d/vfe/dynamic_pillar_vfe.py:88-146): torch.unique over the cell keys (a sort and a host
+ *      read), scatter_mean / scatter_max through torch_scatter (float atomics), the gathers by unq_inv and an [N, 64]
+ *      activation tensor written and read several times.
+ *    Every in-range point is kept: no per-pillar or per-frame cap, no [M, T, C] buffer; a pillar is a ragged list.
+ *    Pillarisation 10 launches, training forward 5, eval forward 3, backward 2.  Integer atomics only (bitmap OR, counts,
+ *    a work list), no float atomics, every floating sum in double in a fixed order: all outputs are bitwise reproducible.  No
+ *    host read: every launch shape depends on host values only.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* points [n_points, stride] fp32, x and y at columns xyz_col, xyz_col + 1, the frame index at batch_col (< 0: frame 0).
+ *   range_lo2 (xmin, ymin), voxel_size2, grid2 (X, Y): HOST arrays.  cx = floor(fl32(fl32(x - xmin) / vx)), cy likewise.
+ * A point is kept iff 0 <= cx < X and 0 <= cy < Y; z is NOT tested (as in the reference); a NaN x or y drops the point.
+ *   A point whose batch column is outside [0, batch) is dropped too: that is the padding convention for static capacity
+ *   (pad a cloud with batch = -1 rows).  The reference does not check the batch column.
+ * Pillars are the unique cells in ascending key (b X + cx) Y + cy, torch.unique's order.  Outputs, device:
+ *   coords [cap, 4] int32 = (b, 0, cy, cx); point_to_pillar [n_points] int32 = torch.unique's inverse, -1 for a dropped
+ *   point or a pillar row >= cap; count [cap] int32 (0 for a dead row); offset [cap + 1] int32 = the exclusive scan of
+ *   count; order [n_points] int32 = point rows grouped by pillar, ascending point row inside a pillar (positions >=
+ *   *d_num_points are not written); d_num_pillars int64[1] = the true pillar count, which may exceed cap (d_status,
+ *   nullable, then receives SPX_ERR_CAPACITY); d_num_points int64[1] = the number of points with point_to_pillar >= 0.
+ *   coords rows >= min(*d_num_pillars, cap) are not written.
+ * batch * X * Y >= 2^31, n_points >= 2^31, cap >= 2^31 - 1: SPX_ERR_TOO_LARGE.  ws: spx_dynamic_pillarize_ws_bytes. */
+size_t spx_dynamic_pillarize_ws_bytes(int64_t n_points, int batch, const int32_t *grid2, int64_t cap);
+int spx_dynamic_pillarize(const float *points, int64_t n_points, int stride, int batch_col, int xyz_col,
+                          const float *range_lo2, const float *voxel_size2, const int32_t *grid2, int batch,
+                          int32_t *coords, int32_t *point_to_pillar, int32_t *count, int32_t *offset, int32_t *order,
+                          int64_t *d_num_pillars, int64_t *d_num_points, int64_t cap, int32_t *d_status, void *ws,
+                          size_t ws_bytes, spx_stream_t stream);
+
+/* Inputs: points as above with the c raw feature columns (x, y, z first, 3 <= c <= 6) at xyz_col .. xyz_col + c - 1;
+ *   coords, point_to_pillar, offset, order, d_num_pillars, d_num_points, cap: what spx_dynamic_pillarize wrote; weight
+ *   [c_out, c_in] fp32, c_in = (use_absolute_xyz ? c + 6 : c + 3) + (with_distance ? 1 : 0) else SPX_ERR_INVALID_ARG;
+ *   c_out != 64: SPX_ERR_UNSUPPORTED; gamma, beta, running_mean, running_var [c_out] fp32, num_batches_tracked int64[1]
+ *   (the three may be NULL in training); geom5: HOST float[5] = voxel size (x, y), then the centre offsets voxel / 2 +
+ *   range_lo (x, y, z).
+ * Features of a kept point, in weight-column order: [x, y, z if use_absolute_xyz | columns 3 .. c - 1 | xyz - pillar
+ *   mean | xyz - centre | |xyz| if with_distance]; the centre of x and y is fl32(fl32(cell * voxel) + offset), the centre
+ *   of z is the constant offset z; the pillar mean is a double sum over `order` in a fixed order (written to pillar_mean
+ *   [cap, 3] doubles, which the backward reads); differences, sums and products are taken in double.
+ * training != 0: batch statistics over the N = *d_num_points kept points, z = (x - mean) * invstd * gamma + beta with the
+ *   biased variance; running_mean / running_var move by `momentum` towards the batch mean / UNBIASED variance,
+ *   num_batches_tracked += 1; save_mean, save_invstd [c_out] fp32 and stats [spx_dynamic_pillar_vfe_stats_len()] doubles
+ *   (G, S1, mean, invstd, N) are written.  N < 2 (torch raises): nothing is divided by zero, the running statistics and
+ *   the counter stay untouched and d_status (nullable) receives SPX_ERR_BATCH_STATS.  training == 0: z from the running
+ *   statistics; save_*, stats unused.
+ * Outputs: out [cap, c_out] = max over the pillar's points of relu(z); arg [cap, c_out] int32 = the winning point's row
+ *   in `points`; equal values take the lowest position in `order`.  Rows >= min(*d_num_pillars, cap) are never
+ *   dereferenced; their out is exact zeros and their arg -1.
+ * ws: spx_dynamic_pillar_vfe_ws_bytes(n_points) bytes (both entry points). */
+size_t spx_dynamic_pillar_vfe_stats_len(void);
+size_t spx_dynamic_pillar_vfe_ws_bytes(int64_t n_points);
+int spx_dynamic_pillar_vfe_fwd(const float *points, int64_t n_points, int stride, int xyz_col, int32_t c,
+                               const int32_t *coords, const int32_t *point_to_pillar, const int32_t *offset,
+                               const int32_t *order, int64_t cap, const int64_t *d_num_pillars,
+                               const int64_t *d_num_points, const float *weight, int32_t c_in, int32_t c_out,
+                               const float *gamma, const float *beta, float *running_mean, float *running_var,
+                               int64_t *num_batches_tracked, float momentum, float eps, const float *geom5,
+                               int use_absolute_xyz, int with_distance, int training, float *out, int32_t *arg,
+                               double *pillar_mean, float *save_mean, float *save_invstd, double *stats,
+                               int32_t *d_status, void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* d_weight [c_out, c_in], d_gamma, d_beta [c_out] from d_out [cap, c_out], every element written.  g = d_out at the point
+ *   arg selects of each live (pillar, channel) with out > 0, 0 on every other of the N points.  training != 0 (stats of
+ *   the forward): d_beta = sum g, d_gamma = sum g xhat, d_weight = gamma invstd [sum g f - (d_beta / N) S1 - (d_gamma / N)
+ *   invstd (G w - mean S1)].  training == 0: d_weight = gamma invstd sum g f on the running statistics.  Points are
+ *   data: no gradient goes to them. */
+int spx_dynamic_pillar_vfe_bwd(const float *points, int64_t n_points, int stride, int xyz_col, int32_t c,
+                               const int32_t *coords, int64_t cap, const int64_t *d_num_pillars, const float *weight,
+                               int32_t c_in, int32_t c_out, const float *gamma, const float *running_mean,
+                               const float *running_var, float eps, const float *geom5, int use_absolute_xyz,
+                               int with_distance, int training, const float *out, const int32_t *arg, const float *d_out,
+                               const double *pillar_mean, const double *stats, float *d_weight, float *d_gamma,
+                               float *d_beta, void *ws, size_t ws_bytes, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ extern "C" const char* spx_strerror(int code) {
     case SPX_ERR_CAPACITY: return "device: more active outputs than the static row capacity of a rule table; rows dropped";
     case SPX_ERR_RING_STALL: return "device: a bounded wait on the weight ring of spx_conv_gemm_ring gave up; output incomplete";
     case SPX_ERR_OUT_OF_GRID: return "device: a live row of spx_voxel_table_build lies outside the table; row skipped";
+    case SPX_ERR_BATCH_STATS: return "device: training-mode batch statistics of fewer than two points; running statistics untouched";
     case SPX_ERR_TABLE_FULL: return "device: hash table full (workspace declared pre-cleared holds stale keys); rows dropped";
     default: return "unknown spx error code";
   }

@@ -184,6 +184,18 @@ SIGNATURES = {
     "spx_pillar_vfe_bwd": (_int, [_vp, _vp, _vp, _i64, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32,
                                   ctypes.c_int32, _vp, _vp, _vp, ctypes.c_float, _f32p, _int, _int, _int, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_dynamic_pillarize_ws_bytes": (_sz, [_i64, _int, _i32p, _i64]),
+    "spx_dynamic_pillarize": (_int, [_vp, _i64, _int, _int, _int, _f32p, _f32p, _i32p, _int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _i64, _vp, _vp, _sz, _vp]),
+    "spx_dynamic_pillar_vfe_stats_len": (_sz, []),
+    "spx_dynamic_pillar_vfe_ws_bytes": (_sz, [_i64]),
+    "spx_dynamic_pillar_vfe_fwd": (_int, [_vp, _i64, _int, _int, ctypes.c_int32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                          ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                          ctypes.c_float, _f32p, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _sz, _vp]),
+    "spx_dynamic_pillar_vfe_bwd": (_int, [_vp, _i64, _int, _int, ctypes.c_int32, _vp, _i64, _vp, _vp, ctypes.c_int32,
+                                          ctypes.c_int32, _vp, _vp, _vp, ctypes.c_float, _f32p, _int, _int, _int, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -2004,3 +2004,223 @@ def pillar_vfe(voxels, num_points, coords, weight, gamma, beta, running_mean, ru
                with_distance=bool(with_distance), training=bool(training), d_n=d_n)
     return _PillarVFEFn.apply(weight, gamma, beta, voxels, num_points, coords, running_mean, running_var,
                               num_batches_tracked, cfg)
+
+
+# ------------------------------------------------------- DynamicPillarVFE: pillarisation + one last-layer PFN (§24)
+
+def _grid2(point_cloud_range, voxel_size):
+    rng = [float(x) for x in point_cloud_range]
+    vs = [float(x) for x in voxel_size]
+    return rng, vs, [int(round((rng[3 + j] - rng[j]) / vs[j])) for j in range(2)]
+
+
+def dynamic_pillarize(points, point_cloud_range, voxel_size, batch_size=1, batch_col=0, xyz_col=1, max_pillars=None,
+                      sync=True):
+    """spx_dynamic_pillarize (include/spx.h §24; reference DynamicPillarVFE.forward's torch.unique): every point with
+    0 <= cx < X and 0 <= cy < Y is kept, z is not tested; NaN x / y and a batch column outside [0, batch_size) drop the
+    point.  Pillars are the unique cells in ascending key (b X + cx) Y + cy.  Returns dict(coords [M, 4] (b, 0, cy, cx),
+    inverse [N] (pillar row of each point, -1 = dropped), count [M], offset [M + 1], order [N] (point rows grouped by
+    pillar, ascending inside a pillar), d_num_pillars, d_num_points (device int64[1]), num_pillars, num_points, grid_size).
+    sync=True reads the two counts (one host read) and trims the rows to M; sync=False reads nothing: rows stay at the
+    capacity min(N, max_pillars), num_pillars / num_points are None, and a pillar count above the capacity raises
+    SPX_ERR_CAPACITY in the device status word (check_status)."""
+    _need_gpu(points)
+    if points.dim() != 2 or points.dtype != torch.float32:
+        raise _lib.SpxError("dynamic_pillarize: points %s %s is not float32 (N, stride)" % (tuple(points.shape), points.dtype))
+    lib = _lib.load()
+    points = points.contiguous()
+    n, stride = points.shape
+    rng, vs, grid = _grid2(point_cloud_range, voxel_size)
+    if min(grid) <= 0 or batch_size <= 0 or xyz_col < 0 or xyz_col + 2 > stride or batch_col >= stride:
+        raise _lib.SpxError("dynamic_pillarize: grid %s, batch_size %d, xyz_col %d, batch_col %d do not fit points of stride "
+                            "%d" % (grid, batch_size, xyz_col, batch_col, stride))
+    cap = max(1, n if max_pillars is None else min(n, int(max_pillars)))
+    dev = points.device
+    coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    inv = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    count = torch.empty((cap,), dtype=torch.int32, device=dev)
+    offset = torch.empty((cap + 1,), dtype=torch.int32, device=dev)
+    order = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    d_num = torch.zeros((2,), dtype=torch.int64, device=dev)
+    g2 = (ctypes.c_int32 * 2)(*grid)
+    wsb = lib.spx_dynamic_pillarize_ws_bytes(n, batch_size, g2, cap)
+    ws = workspace(dev, wsb)
+    status = None if sync else status_word(dev)
+    check(lib.spx_dynamic_pillarize(_ptr(points), n, stride, batch_col, xyz_col, f_arr(rng[:2]), f_arr(vs[:2]), g2,
+                                    batch_size, _ptr(coords), _ptr(inv), _ptr(count), _ptr(offset), _ptr(order),
+                                    _ptr(d_num[0:1]), _ptr(d_num[1:2]), cap, _ptr(status), _ptr(ws), wsb, _stream(points)),
+          "spx_dynamic_pillarize")
+    out = {"d_num_pillars": d_num[0:1], "d_num_points": d_num[1:2], "grid_size": grid, "inverse": inv[:n], "order": order[:n]}
+    if sync:
+        m, kept = d_num.tolist()
+        m = min(int(m), cap)
+        out.update(coords=coords[:m], count=count[:m], offset=offset[:m + 1], num_pillars=m, num_points=int(kept))
+    else:
+        out.update(coords=coords, count=count, offset=offset, num_pillars=None, num_points=None)
+    return out
+
+
+def _dyn_pillar_inputs(what, points, pillars, weight, use_absolute_xyz, with_distance, xyz_col, num_features):
+    """Shape, dtype and device checks shared by the two entry points."""
+    if points.dim() != 2 or points.dtype != torch.float32:
+        raise _lib.SpxError("%s: points %s %s is not float32 (N, stride)" % (what, tuple(points.shape), points.dtype))
+    n, stride = points.shape
+    dev = points.device
+    c = (stride - xyz_col) if num_features is None else int(num_features)
+    if not 3 <= c <= 6 or xyz_col < 0 or xyz_col + c > stride:
+        raise _lib.SpxError("%s: %d raw columns from column %d of %d: outside 3 <= C <= 6" % (what, c, xyz_col, stride))
+    coords = pillars["coords"]
+    cap = coords.shape[0]
+    for name, shape in (("coords", (cap, 4)), ("offset", (cap + 1,)), ("inverse", (n,)), ("order", (n,))):
+        t = pillars[name]
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise _lib.SpxError("%s: pillars[%r] %s %s on %s is not a contiguous int32 %s on %s"
+                                % (what, name, tuple(t.shape), t.dtype, t.device, shape, dev))
+    if cap < 1:
+        raise _lib.SpxError("%s: no pillar rows (a cloud with no kept point has no batch statistics and no output)" % what)
+    d_np = _d_n("%s: d_num_pillars" % what, pillars["d_num_pillars"], dev)
+    d_npts = _d_n("%s: d_num_points" % what, pillars["d_num_points"], dev)
+    c_in = pillar_vfe_c_in(c, use_absolute_xyz, with_distance)
+    if weight.dim() != 2 or weight.shape[1] != c_in or weight.dtype != torch.float32 or weight.device != dev:
+        raise _lib.SpxError("%s: weight %s %s is not float32 (C_out, %d) on %s: C = %d, use_absolute_xyz = %s, "
+                            "with_distance = %s" % (what, tuple(weight.shape), weight.dtype, c_in, dev, c,
+                                                    bool(use_absolute_xyz), bool(with_distance)))
+    if weight.shape[0] != PILLAR_VFE_C_OUT:
+        raise _lib.SpxError("%s: C_out = %d is not supported, the kernels are built for C_out = %d"
+                            % (what, weight.shape[0], PILLAR_VFE_C_OUT))
+    return points.contiguous(), weight.detach().contiguous(), d_np, d_npts, n, stride, c, c_in, cap
+
+
+def _dyn_pillar_geom(voxel_size, offsets):
+    return f_arr([float(voxel_size[0]), float(voxel_size[1])] + [float(v) for v in offsets])
+
+
+def dynamic_pillar_vfe_fwd(points, pillars, weight, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
+                           eps, voxel_size, offsets, use_absolute_xyz=True, with_distance=False, training=False, xyz_col=1,
+                           num_features=None):
+    """spx_dynamic_pillar_vfe_fwd (include/spx.h §24): DynamicPillarVFE with one last-layer PFNLayerV2 over the ragged
+    pillars of dynamic_pillarize (`pillars`: its dict, synced or at capacity), without the (N, 64) activations.  points
+    (N, stride) float32 with the raw columns (x, y, z first) from xyz_col; offsets = voxel / 2 + range_lo (x, y, z).
+    training: batch statistics over the kept points, and running_mean / running_var / num_batches_tracked are updated IN
+    PLACE; fewer than two kept points leave them untouched and raise SPX_ERR_BATCH_STATS in the device status word.
+    Returns dict(out (M, 64), arg (M, 64) int32: the winning point row of each (pillar, channel), pillar_mean (M, 3)
+    float64; mean, invstd (64,) and stats (double, for dynamic_pillar_vfe_bwd) in training, else None).  No host read."""
+    what = "dynamic_pillar_vfe_fwd"
+    _need_gpu(points, weight, gamma, beta, running_mean, running_var, num_batches_tracked, pillars["coords"])
+    lib = _lib.load()
+    points, weight, d_np, d_npts, n, stride, c, c_in, cap = _dyn_pillar_inputs(
+        what, points, pillars, weight, use_absolute_xyz, with_distance, xyz_col, num_features)
+    dev = points.device
+    gamma = _vec64(what, "gamma", gamma.detach(), dev)
+    beta = _vec64(what, "beta", beta.detach(), dev)
+    running_mean = _vec64(what, "running_mean", running_mean, dev)
+    running_var = _vec64(what, "running_var", running_var, dev)
+    nbt = None
+    if num_batches_tracked is not None:
+        nbt = _vec64(what, "num_batches_tracked", num_batches_tracked.view(-1), dev, torch.int64, 1)
+    if not training and (running_mean is None or running_var is None):
+        raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    out = torch.empty((cap, PILLAR_VFE_C_OUT), dtype=torch.float32, device=dev)
+    arg = torch.empty((cap, PILLAR_VFE_C_OUT), dtype=torch.int32, device=dev)
+    pmean = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+    mean = invstd = stats = None
+    if training:
+        mean = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+        invstd = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+        stats = torch.empty((int(lib.spx_dynamic_pillar_vfe_stats_len()),), dtype=torch.float64, device=dev)
+    wsb = lib.spx_dynamic_pillar_vfe_ws_bytes(n)
+    ws = workspace(dev, wsb)
+    check(lib.spx_dynamic_pillar_vfe_fwd(
+        _ptr(points), n, stride, xyz_col, c, _ptr(pillars["coords"]), _ptr(pillars["inverse"]), _ptr(pillars["offset"]),
+        _ptr(pillars["order"]), cap, _ptr(d_np), _ptr(d_npts), _ptr(weight), c_in, weight.shape[0], _ptr(gamma), _ptr(beta),
+        _ptr(running_mean), _ptr(running_var), _ptr(nbt), float(momentum), float(eps), _dyn_pillar_geom(voxel_size, offsets),
+        1 if use_absolute_xyz else 0, 1 if with_distance else 0, 1 if training else 0, _ptr(out), _ptr(arg), _ptr(pmean),
+        _ptr(mean), _ptr(invstd), _ptr(stats), _ptr(status_word(dev)), _ptr(ws), wsb, _stream(points)),
+        "spx_dynamic_pillar_vfe_fwd")
+    return dict(out=out, arg=arg, pillar_mean=pmean, mean=mean, invstd=invstd, stats=stats)
+
+
+def dynamic_pillar_vfe_bwd(d_out, out, arg, pillar_mean, stats, points, pillars, weight, gamma, running_mean, running_var,
+                           eps, voxel_size, offsets, use_absolute_xyz=True, with_distance=False, training=True, xyz_col=1,
+                           num_features=None):
+    """spx_dynamic_pillar_vfe_bwd: (d_weight (64, C_in), d_gamma (64,), d_beta (64,)) from d_out (M, 64) and what
+    dynamic_pillar_vfe_fwd returned (out, arg, pillar_mean, and stats in training): the exact train-mode BatchNorm
+    gradient (eval: on the running statistics) from the selected points alone.  Deterministic, no host read."""
+    what = "dynamic_pillar_vfe_bwd"
+    _need_gpu(d_out, out, arg, pillar_mean, stats, points, weight, gamma, running_mean, running_var)
+    lib = _lib.load()
+    points, weight, d_np, _d_npts, n, stride, c, c_in, cap = _dyn_pillar_inputs(
+        what, points, pillars, weight, use_absolute_xyz, with_distance, xyz_col, num_features)
+    dev = points.device
+    shape = (cap, PILLAR_VFE_C_OUT)
+    if tuple(d_out.shape) != shape or d_out.device != dev or tuple(out.shape) != shape or out.dtype != torch.float32 \
+            or tuple(arg.shape) != shape or arg.dtype != torch.int32 or tuple(pillar_mean.shape) != (cap, 3) \
+            or pillar_mean.dtype != torch.float64:
+        raise _lib.SpxError("%s: d_out %s, out %s %s, arg %s %s, pillar_mean %s %s do not match float32 / float32 / int32 %s "
+                            "and float64 (%d, 3)" % (what, tuple(d_out.shape), tuple(out.shape), out.dtype, tuple(arg.shape),
+                                                     arg.dtype, tuple(pillar_mean.shape), pillar_mean.dtype, shape, cap))
+    d_out, out, arg, pillar_mean = _f32(d_out), out.contiguous(), arg.contiguous(), pillar_mean.contiguous()
+    gamma = _vec64(what, "gamma", gamma.detach(), dev)
+    if training:
+        stats = _vec64(what, "stats", stats, dev, torch.float64, int(lib.spx_dynamic_pillar_vfe_stats_len()))
+        if stats is None:
+            raise _lib.SpxError("%s: training mode needs the forward's stats" % what)
+    else:
+        running_mean = _vec64(what, "running_mean", running_mean, dev)
+        running_var = _vec64(what, "running_var", running_var, dev)
+        if running_mean is None or running_var is None:
+            raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    d_weight = torch.empty_like(weight)
+    d_gamma = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    d_beta = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    wsb = lib.spx_dynamic_pillar_vfe_ws_bytes(n)
+    ws = workspace(dev, wsb)
+    check(lib.spx_dynamic_pillar_vfe_bwd(
+        _ptr(points), n, stride, xyz_col, c, _ptr(pillars["coords"]), cap, _ptr(d_np), _ptr(weight), c_in, weight.shape[0],
+        _ptr(gamma), _ptr(running_mean), _ptr(running_var), float(eps), _dyn_pillar_geom(voxel_size, offsets),
+        1 if use_absolute_xyz else 0, 1 if with_distance else 0, 1 if training else 0, _ptr(out), _ptr(arg), _ptr(d_out),
+        _ptr(pillar_mean), _ptr(stats) if training else None, _ptr(d_weight), _ptr(d_gamma), _ptr(d_beta), _ptr(ws), wsb,
+        _stream(points)), "spx_dynamic_pillar_vfe_bwd")
+    return d_weight, d_gamma, d_beta
+
+
+class _DynPillarVFEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, gamma, beta, points, running_mean, running_var, nbt, pillars, cfg):
+        res = dynamic_pillar_vfe_fwd(points, pillars, weight, gamma, beta, running_mean, running_var, nbt, cfg["momentum"],
+                                     cfg["eps"], cfg["voxel_size"], cfg["offsets"], cfg["use_absolute_xyz"],
+                                     cfg["with_distance"], cfg["training"], cfg["xyz_col"], cfg["num_features"])
+        ctx.cfg = cfg
+        ctx.inputs = (points, pillars, running_mean, running_var)
+        ctx.save_for_backward(weight, gamma, res["out"], res["arg"], res["pillar_mean"],
+                              *([res["stats"]] if cfg["training"] else []))
+        ctx.mark_non_differentiable(res["arg"])
+        return res["out"], res["arg"]
+
+    @staticmethod
+    def backward(ctx, d_out, _d_arg):
+        cfg = ctx.cfg
+        weight, gamma, out, arg, pmean = ctx.saved_tensors[:5]
+        stats = ctx.saved_tensors[5] if cfg["training"] else None
+        points, pillars, running_mean, running_var = ctx.inputs
+        dw, dg, db = dynamic_pillar_vfe_bwd(d_out, out, arg, pmean, stats, points, pillars, weight, gamma, running_mean,
+                                            running_var, cfg["eps"], cfg["voxel_size"], cfg["offsets"],
+                                            cfg["use_absolute_xyz"], cfg["with_distance"], cfg["training"], cfg["xyz_col"],
+                                            cfg["num_features"])
+        return dw, dg, db, None, None, None, None, None, None
+
+
+def dynamic_pillar_vfe(points, pillars, weight, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                       voxel_size, offsets, use_absolute_xyz=True, with_distance=False, training=False, xyz_col=1,
+                       num_features=None):
+    """The differentiable form of dynamic_pillar_vfe_fwd / _bwd: (pillar_features (M, 64), arg (M, 64) int32) with
+    gradients for weight, gamma and beta.  In eval mode the running statistics are read a second time by the backward, so
+    they must not change in between.  Points are data: there is no gradient with respect to them."""
+    if points.requires_grad:
+        raise _lib.SpxError("dynamic_pillar_vfe: points.requires_grad is set, but the op has no gradient with respect to "
+                            "points")
+    cfg = dict(momentum=float(momentum), eps=float(eps), voxel_size=[float(v) for v in voxel_size],
+               offsets=[float(v) for v in offsets], use_absolute_xyz=bool(use_absolute_xyz),
+               with_distance=bool(with_distance), training=bool(training), xyz_col=int(xyz_col),
+               num_features=None if num_features is None else int(num_features))
+    return _DynPillarVFEFn.apply(weight, gamma, beta, points, running_mean, running_var, num_batches_tracked, pillars, cfg)
