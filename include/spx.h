@@ -1117,6 +1117,63 @@ int spx_dynamic_pillar_vfe_bwd(const float *points, int64_t n_points, int stride
                                const double *pillar_mean, const double *stats, float *d_weight, float *d_gamma,
                                float *d_beta, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 25. Rotated RoI bilinear pooling of a BEV map (csrc/roi_grid_pool.hip)
+ *    replaces: SECONDHead.roi_grid_pool (reference pcdet/models/roi_heads/second_head.py:53-110): a loop over frames
+ *      with affine_grid + grid_sample on a (num_rois, C, H, W) expanded view.  One launch, forward only: the reference
+ *      detaches both the RoIs and the map, so no gradient exists.  No host read, no atomics.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* rois [batch, n_rois, roi_stride] fp32 (x, y, z, dx, dy, dz, heading, ...), roi_stride >= 7; features: fp32 map of
+ *   batch x c x h x w elements addressed by the four element strides (dense NCHW, channels_last, or any view), h, w >= 2;
+ *   d_n: device int64[1] live row count over the batch * n_rois rows (clamped) or NULL = all; min_x, min_y: the range's
+ *   lower corner; step_x, step_y > 0: metres per map pixel (voxel size * downsample ratio).
+ * Per RoI, in double: x1 = (x - dx / 2 - min_x) / step_x, x2 = (x + dx / 2 - min_x) / step_x, y1, y2 likewise; theta =
+ *   [(x2 - x1) / (w - 1) cos a, -(x2 - x1) / (w - 1) sin a, (x1 + x2 - w + 1) / (w - 1); (y2 - y1) / (h - 1) sin a,
+ *   (y2 - y1) / (h - 1) cos a, (y1 + y2 - h + 1) / (h - 1)], each entry ROUNDED TO fp32.  Cell (i, j) of the grid_size^2
+ *   grid has base coordinates bx = (2 j + 1) / G - 1, by = (2 i + 1) / G - 1, sample point g = theta (bx, by, 1) and
+ *   pixel coordinates ((gx + 1) w - 1) / 2, ((gy + 1) h - 1) / 2 (affine_grid and grid_sample with align_corners =
+ *   False), bilinear, taps outside the map contribute 0: a cell whose four taps are all outside is exactly 0.
+ * out [batch * n_rois, c, G, G] fp32, contiguous; every element is written; rows >= the live count are zeros and their
+ *   RoIs are not read.  grid_size > 12: SPX_ERR_UNSUPPORTED.  batch * n_rois == 0: SPX_OK, nothing launched. */
+int spx_roi_grid_pool_bev(const float *rois, int32_t batch, int64_t n_rois, int32_t roi_stride, const int64_t *d_n,
+                          const float *features, int32_t c, int32_t h, int32_t w, int64_t stride_b, int64_t stride_c,
+                          int64_t stride_h, int64_t stride_w, int32_t grid_size, double min_x, double min_y,
+                          double step_x, double step_y, float *out, spx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 26. Second-stage proposal sampling: RoI / GT matching and fg / bg sampling (csrc/proposal_targets.hip)
+ *    replaces: ProposalTargetLayer.sample_rois_for_rcnn, subsample_rois, sample_bg_inds, get_max_iou_with_same_class
+ *      (reference pcdet/models/roi_heads/target_assigner/proposal_target_layer.py:64-228): loops over frames and
+ *      classes with nonzero / numel / item host reads and numpy / CPU-torch random numbers.
+ *    Two launches for the batch.  The random draws are inputs.  One integer LDS atomic, no float atomics, no host read:
+ *    the outputs are a pure function of the inputs, bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* rois [batch, r, roi_stride] fp32, roi_stride >= 7; roi_labels [batch, r] int64; gt_boxes [batch, gmax, gt_stride] fp32,
+ *   gt_stride >= 8, the class in the LAST column; 1 <= r <= 2048 else SPX_ERR_TOO_LARGE; gmax >= 1.
+ *   fg_keys [batch, r] fp32: one sort key per RoI; slot_u [batch, m] fp32 in [0, 1): one draw per output slot.
+ * Per frame: trailing GT rows whose fp32 column sum (in column order) is 0 are dropped; row 0 always stays, interior zero
+ *   rows stay.  The 3-D IoU of a pair is BEV overlap (box_iou.h overlap_area(roi, gt)) x height overlap / max(union
+ *   volume, 1e-6), in fp32.  A RoI takes the GT row of largest IoU, the lowest row on ties; with by_class only rows
+ *   whose class, truncated to an integer, equals its label count, a RoI with no such row gets overlap 0 and row 0, and
+ *   one whose rows all have IoU 0 gets the first of them.
+ * Candidates, by overlap o: fg o >= min(reg_fg, cls_fg); hard bg bg_lo <= o < reg_fg; easy bg o < bg_lo (fg and hard
+ *   overlap when reg_fg > cls_fg), each list in ascending RoI order, sizes n_fg, n_hard, n_easy.  Output slots:
+ *   n_fg > 0 and bg exists: the first min(fg_per_image, n_fg) fg candidates in ascending (fg_keys, RoI index) order, then
+ *     the bg slots; no fg: m bg slots.  bg slots: hard first, min((int)(slots * hard_bg_ratio), n_hard) of them when both
+ *     kinds exist (the product in double), all of them when only hard exists, then easy.
+ *   n_fg > 0 and no bg: m fg slots with replacement.
+ *   A slot with replacement at position s takes entry min(floor(slot_u[s] * n), n - 1) of its list of n (in double).
+ * Outputs [batch, m]: sampled_inds int64 (RoI row in the frame), roi_ious fp32, gt_inds int64 (GT row in the frame).
+ * ws: spx_proposal_sample_ws_bytes(batch, r, gmax) bytes.  batch == 0: SPX_OK, nothing launched. */
+size_t spx_proposal_sample_ws_bytes(int32_t batch, int32_t r, int32_t gmax);
+int spx_proposal_sample(const float *rois, const int64_t *roi_labels, const float *gt_boxes, int32_t batch, int32_t r,
+                        int32_t roi_stride, int32_t gmax, int32_t gt_stride, int32_t m, int32_t fg_per_image,
+                        float reg_fg_thresh, float cls_fg_thresh, float cls_bg_thresh_lo, double hard_bg_ratio,
+                        int by_class, const float *fg_keys, const float *slot_u, int64_t *sampled_inds, float *roi_ious,
+                        int64_t *gt_inds, void *ws, size_t ws_bytes, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,21 @@ class SyntheticDataset(Dataset):
         if 'max_voxels' in spec:
             self.max_voxels = {'train': spec['max_voxels'], 'test': spec['max_voxels']}
         self.length = length
+        self.dataset_cfg = self._geometry_cfg(dataset_cfg)
+
+    def _geometry_cfg(self, dataset_cfg):
+        """The dataset_cfg a second-stage head reads (reference second_head.py:68-72: POINT_CLOUD_RANGE and the last
+        DATA_PROCESSOR's VOXEL_SIZE), always that of the grid the model is built on: a copy of the given config whose two
+        entries are this dataset's own range and voxel size (cfg_id may select a geometry other than the yaml's)."""
+        from ..config import AttrDict
+        out = AttrDict(dataset_cfg or {})
+        procs = [p for p in out.get('DATA_PROCESSOR', None) or []]
+        has_voxel_size = bool(procs) and 'VOXEL_SIZE' in procs[-1]
+        last = AttrDict(procs[-1]) if has_voxel_size else AttrDict(NAME='transform_points_to_voxels_placeholder')
+        last['VOXEL_SIZE'] = [float(v) for v in self.voxel_size]
+        out['DATA_PROCESSOR'] = (procs[:-1] if has_voxel_size else procs) + [last]
+        out['POINT_CLOUD_RANGE'] = [float(v) for v in self.point_cloud_range]
+        return out
 
     def __len__(self):
         return self.length

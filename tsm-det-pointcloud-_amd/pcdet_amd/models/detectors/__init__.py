@@ -3,10 +3,12 @@ from .detector3d_template import Detector3DTemplate
 from .point_3dssd import Point3DSSD
 from .pointpillar import PointPillar
 from .second_net import SECONDNet
+from .second_net_iou import SECONDNetIoU
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'SECONDNet': SECONDNet,
+    'SECONDNetIoU': SECONDNetIoU,
     '3DSSD': Point3DSSD,
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,

@@ -5,7 +5,8 @@ Differences forced by the fork's drift, all backwards compatible
   * build_backbone_2d keeps `num_bev_features` from the module's own attribute (falls back to the fork's
     num_voxel_neck_features) and never overwrites num_point_features with None;
   * POST_PROCESSING.SCORE_THRESH may be a scalar (upstream) or a per-class list (fork's multi_thresh).
-Only the module slots of the SECOND and 3DSSD paths are populated; the other slots of `module_topology` stay None.
+Only the module slots of the SECOND, SECOND-IoU and 3DSSD paths are populated; the other slots of `module_topology`
+stay None.
 """
 import os
 
@@ -13,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from ...utils.spconv_utils import find_all_spconv_keys
-from .. import backbones_2d, backbones_3d, dense_heads
+from .. import backbones_2d, backbones_3d, dense_heads, roi_heads
 from ..backbones_2d import map_to_bev
 from ..backbones_3d import vfe
 from ..model_utils import model_nms_utils
@@ -139,7 +140,20 @@ class Detector3DTemplate(nn.Module):
         return m, model_info_dict
 
     def build_roi_head(self, model_info_dict):
-        return self._absent('ROI_HEAD', model_info_dict)
+        if self.model_cfg.get('ROI_HEAD', None) is None:
+            return None, model_info_dict
+        name = self.model_cfg.ROI_HEAD.NAME
+        if name not in roi_heads.__all__ or name == 'RoIHeadTemplate':
+            raise NotImplementedError('ROI_HEAD %s is not supported (second-stage heads: %s)'
+                                      % (name, ', '.join(k for k in roi_heads.__all__ if k != 'RoIHeadTemplate')))
+        m = roi_heads.__all__[name](
+            model_cfg=self.model_cfg.ROI_HEAD, input_channels=model_info_dict['num_point_features'],
+            backbone_channels=model_info_dict.get('backbone_channels', None),
+            point_cloud_range=model_info_dict['point_cloud_range'], voxel_size=model_info_dict['voxel_size'],
+            grid_size=model_info_dict['grid_size'],
+            num_class=self.num_class if not self.model_cfg.ROI_HEAD.CLASS_AGNOSTIC else 1)
+        model_info_dict['module_list'].append(m)
+        return m, model_info_dict
 
     def forward(self, **kwargs):
         raise NotImplementedError

@@ -24,6 +24,19 @@ def limit_period(val, offset=0.5, period=np.pi):
     return out.numpy() if is_np else out
 
 
+def rotate_points_along_z(points, angle):
+    """points (B, N, 3 + C) rotated about z by angle (B), the angle growing from x to y (reference common_utils.py:41-63).
+    The rotation matrix is rounded to float32 as the reference's `.float()` does, then used in the points' dtype."""
+    points, is_numpy = check_numpy_to_torch(points)
+    angle, _ = check_numpy_to_torch(angle)
+    cosa, sina = torch.cos(angle), torch.sin(angle)
+    zeros, ones = angle.new_zeros(points.shape[0]), angle.new_ones(points.shape[0])
+    rot_matrix = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
+    points_rot = torch.matmul(points[:, :, 0:3], rot_matrix.to(points.dtype))
+    points_rot = torch.cat((points_rot, points[:, :, 3:]), dim=-1)
+    return points_rot.numpy() if is_numpy else points_rot
+
+
 def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_range):
     """(z,y,x) voxel indices -> metric xyz centres (reference common_utils.py:73-89)."""
     assert voxel_coords.shape[1] == 3

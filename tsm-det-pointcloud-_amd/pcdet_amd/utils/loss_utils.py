@@ -6,6 +6,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import common_utils
+
 
 class SigmoidFocalClassificationLoss(nn.Module):
     def __init__(self, gamma=2.0, alpha=0.25):
@@ -238,3 +240,34 @@ class RegLossCenterNet(nn.Module):
             from ..models.model_utils.centernet_utils import _transpose_and_gather_feat
             pred = _transpose_and_gather_feat(output, ind)
         return _reg_loss(pred, target, mask)
+
+
+def _corners_3d(boxes3d):
+    """(N, 7) -> (N, 8, 3) corners in the boxes' own dtype, the reference's boxes_to_corners_3d (box_utils.py:28-53)."""
+    template = boxes3d.new_tensor([[1, 1, -1], [1, -1, -1], [-1, -1, -1], [-1, 1, -1],
+                                   [1, 1, 1], [1, -1, 1], [-1, -1, 1], [-1, 1, 1]]) / 2
+    corners = boxes3d[:, None, 3:6] * template[None]
+    corners = common_utils.rotate_points_along_z(corners, boxes3d[:, 6])
+    return corners + boxes3d[:, None, 0:3]
+
+
+def get_corner_loss_lidar(pred_bbox3d, gt_bbox3d):
+    """(N, 7), (N, 7) -> (N): smooth-L1 (beta 1) of the eight corner distances, the smaller of the distance to the ground
+    truth and to the ground truth turned by pi, averaged over the corners (reference loss_utils.py:365-388)."""
+    assert pred_bbox3d.shape[0] == gt_bbox3d.shape[0]
+    pred_corners = _corners_3d(pred_bbox3d)
+    gt_corners = _corners_3d(gt_bbox3d)
+    gt_flip = torch.cat([gt_bbox3d[:, :6], gt_bbox3d[:, 6:7] + np.pi, gt_bbox3d[:, 7:]], dim=1)
+    gt_corners_flip = _corners_3d(gt_flip)
+    dist = torch.min(torch.norm(pred_corners - gt_corners, dim=2), torch.norm(pred_corners - gt_corners_flip, dim=2))
+    return WeightedSmoothL1Loss.smooth_l1_loss(dist, beta=1.0).mean(dim=1)
+
+
+def sigmoid_focal_cls_loss(input, target, gamma=2.0, alpha=0.25):
+    """Element-wise sigmoid focal loss on logits with soft targets in [0, 1].  SECONDHead's IOU_LOSS 'focalbce' calls this
+    name (reference second_head.py:169), but neither the fork nor upstream OpenPCDet defines it; this is
+    SigmoidFocalClassificationLoss (:9-77) with unit weights, its defaults gamma 2 and alpha 0.25."""
+    p = torch.sigmoid(input)
+    alpha_w = target * alpha + (1 - target) * (1 - alpha)
+    pt = target * (1.0 - p) + (1.0 - target) * p
+    return alpha_w * torch.pow(pt, gamma) * SigmoidFocalClassificationLoss.sigmoid_cross_entropy_with_logits(input, target)

@@ -196,6 +196,12 @@ SIGNATURES = {
     "spx_dynamic_pillar_vfe_bwd": (_int, [_vp, _i64, _int, _int, ctypes.c_int32, _vp, _i64, _vp, _vp, ctypes.c_int32,
                                           ctypes.c_int32, _vp, _vp, _vp, ctypes.c_float, _f32p, _int, _int, _int, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_roi_grid_pool_bev": (_int, [_vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int32, _i64, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    "spx_proposal_sample_ws_bytes": (_sz, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "spx_proposal_sample": (_int, [_vp, _vp, _vp] + [ctypes.c_int32] * 7 + [ctypes.c_float] * 3 +
+                            [ctypes.c_double, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

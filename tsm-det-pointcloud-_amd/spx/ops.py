@@ -2224,3 +2224,71 @@ def dynamic_pillar_vfe(points, pillars, weight, gamma, beta, running_mean, runni
                with_distance=bool(with_distance), training=bool(training), xyz_col=int(xyz_col),
                num_features=None if num_features is None else int(num_features))
     return _DynPillarVFEFn.apply(weight, gamma, beta, points, running_mean, running_var, num_batches_tracked, pillars, cfg)
+
+
+# ------------------------------------------------------------------------------ second stage: RoI pooling, sampling (§25, §26)
+
+ROI_GRID_POOL_MAX_G = 12
+PROPOSAL_SAMPLE_MAX_R = 2048
+
+
+def roi_grid_pool_bev(rois, features, grid_size, min_x, min_y, step_x, step_y, d_n=None):
+    """spx_roi_grid_pool_bev: rois (B, N, >= 7) fp32, features (B, C, H, W) fp32 in any strided layout (dense NCHW and
+    channels_last are read without a copy), step = voxel size * downsample ratio -> (B * N, C, G, G) fp32, the reference's
+    SECONDHead.roi_grid_pool.  d_n: optional int64[1] live row count over the B * N rows; rows past it are zeros.  Forward
+    only: neither input receives a gradient (the reference detaches both).  No host read."""
+    _need_gpu(rois, features)
+    lib = _lib.load()
+    if rois.dim() != 3 or rois.shape[2] < 7 or features.dim() != 4 or features.shape[0] != rois.shape[0] \
+            or rois.dtype != torch.float32 or features.dtype != torch.float32:
+        raise _lib.SpxError("roi_grid_pool_bev: rois %s (%s), features %s (%s) do not match"
+                            % (tuple(rois.shape), rois.dtype, tuple(features.shape), features.dtype))
+    rois = rois.detach().contiguous()
+    features = features.detach()
+    b, n, rs = rois.shape
+    _, c, h, w = features.shape
+    g = int(grid_size)
+    sb, sc, sh, sw = features.stride()
+    if min(sc, sh, sw) < 1 or sb < 0:                 # an expanded (stride 0) view has no single element per index
+        features = features.contiguous()
+        sb, sc, sh, sw = features.stride()
+    d_n = _d_n("roi_grid_pool_bev: d_n", d_n, rois.device)
+    out = torch.empty((b * n, c, g, g), dtype=torch.float32, device=rois.device)
+    check(lib.spx_roi_grid_pool_bev(_ptr(rois), b, n, rs, _ptr(d_n), _ptr(features), c, h, w, sb, sc, sh, sw, g,
+                                    float(min_x), float(min_y), float(step_x), float(step_y), _ptr(out), _stream(rois)),
+          "spx_roi_grid_pool_bev")
+    return out
+
+
+def proposal_sample(rois, roi_labels, gt_boxes, roi_per_image, fg_per_image, reg_fg_thresh, cls_fg_thresh,
+                    cls_bg_thresh_lo, hard_bg_ratio, by_class, fg_keys, slot_u):
+    """spx_proposal_sample: rois (B, R, >= 7) fp32, roi_labels (B, R) int64, gt_boxes (B, G, >= 8) fp32 with the class
+    last, fg_keys (B, R) and slot_u (B, M) fp32 uniform draws -> sampled_inds (B, M) int64, roi_ious (B, M) fp32, gt_inds
+    (B, M) int64: the reference's ProposalTargetLayer.sample_rois_for_rcnn with its random numbers as inputs
+    (include/spx.h §26).  fg_per_image = int(round(FG_RATIO * M)).  No host read."""
+    _need_gpu(rois, roi_labels, gt_boxes, fg_keys, slot_u)
+    lib = _lib.load()
+    m = int(roi_per_image)
+    if rois.dim() != 3 or rois.shape[2] < 7 or gt_boxes.dim() != 3 or gt_boxes.shape[2] < 8 or rois.shape[1] < 1 \
+            or gt_boxes.shape[0] != rois.shape[0] or tuple(roi_labels.shape) != tuple(rois.shape[:2]) \
+            or tuple(fg_keys.shape) != tuple(rois.shape[:2]) or tuple(slot_u.shape) != (rois.shape[0], m):
+        raise _lib.SpxError("proposal_sample: rois %s, roi_labels %s, gt_boxes %s, fg_keys %s, slot_u %s do not match"
+                            % (tuple(rois.shape), tuple(roi_labels.shape), tuple(gt_boxes.shape), tuple(fg_keys.shape),
+                               tuple(slot_u.shape)))
+    rois, gt_boxes, fg_keys, slot_u = _f32(rois), _f32(gt_boxes), _f32(fg_keys), _f32(slot_u)
+    roi_labels = roi_labels.to(torch.int64).contiguous()
+    b, r, rs = rois.shape
+    if gt_boxes.shape[1] == 0:                        # the reference samples against one all-zero row
+        gt_boxes = gt_boxes.new_zeros((b, 1, gt_boxes.shape[2]))
+    gmax, gs = gt_boxes.shape[1], gt_boxes.shape[2]
+    dev = rois.device
+    sampled = torch.empty((b, m), dtype=torch.int64, device=dev)
+    ious = torch.empty((b, m), dtype=torch.float32, device=dev)
+    gt_inds = torch.empty((b, m), dtype=torch.int64, device=dev)
+    wsb = lib.spx_proposal_sample_ws_bytes(b, r, gmax)
+    ws = workspace(dev, wsb)
+    check(lib.spx_proposal_sample(_ptr(rois), _ptr(roi_labels), _ptr(gt_boxes), b, r, rs, gmax, gs, m, int(fg_per_image),
+                                  float(reg_fg_thresh), float(cls_fg_thresh), float(cls_bg_thresh_lo), float(hard_bg_ratio),
+                                  int(bool(by_class)), _ptr(fg_keys), _ptr(slot_u), _ptr(sampled), _ptr(ious),
+                                  _ptr(gt_inds), _ptr(ws), wsb, _stream(rois)), "spx_proposal_sample")
+    return sampled, ious, gt_inds
