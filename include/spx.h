@@ -1174,6 +1174,51 @@ int spx_proposal_sample(const float *rois, const int64_t *roi_labels, const floa
                         int by_class, const float *fg_keys, const float *slot_u, int64_t *sampled_inds, float *roi_ious,
                         int64_t *gt_inds, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 27. Voxel-grid max pooling: the tail of NeighborVoxelSAModuleMSG after the voxel query (csrc/voxel_pool.hip)
+ *    replaces: the gather of (M, C, nsample) features, masked_fill, the position Conv2d + BatchNorm2d on the
+ *      (M, 3, nsample) offsets, the add, ReLU and max over the slots (reference
+ *      pcdet/ops/pointnet2/pointnet2_stack/voxel_pool_modules.py, max_pool), forward and backward.  BatchNorm is NOT in
+ *      here: the caller folds it into the affine map (a, b) from the moments below.
+ *    Queries m in [0, m); slots s in [0, nsample); source row r = idx[m, s] (GLOBAL rows); e = empty[m] != 0 (empty may
+ *    be NULL: none).  d(m, s) = xyz[r] - new_xyz[m], three fp32 subtractions, or (0, 0, 0) when e.  idx of an empty
+ *    query is never read.  A slot whose r is outside [0, n_src) is SKIPPED, never dereferenced; a query whose slots are
+ *    all skipped behaves as empty.  Any c >= 1, nsample >= 1.  No host read, no float atomics, bitwise reproducible,
+ *    capturable.  m * nsample, m * c >= 2^31 - 1: SPX_ERR_TOO_LARGE.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* xyz [n_src, 3], new_xyz [m, 3], idx [m, nsample] int32, empty [m] bytes -> moments double[9] on the device:
+ *   (sum dx, sum dy, sum dz, sum dx dx, dx dy, dx dz, dy dy, dy dz, dz dz) over all m * nsample columns, d promoted to
+ *   double after the fp32 subtraction; empty queries and skipped slots are zero columns, repeated slots count every time.
+ *   DETERMINISTIC: per-block partials over chunks of 2048 columns, then a fixed-order sum of the partials.
+ *   ws: spx_voxel_pool_moments_ws_bytes bytes. */
+size_t spx_voxel_pool_moments_ws_bytes(int64_t m, int32_t nsample);
+int spx_voxel_pool_moments(const float *xyz, const float *new_xyz, const int32_t *idx, const uint8_t *empty,
+                           int64_t n_src, int64_t m, int32_t nsample, double *moments, void *ws, size_t ws_bytes,
+                           spx_stream_t stream);
+
+/* f [n_src, c], a [c, 3], b [c] -> out [m, c] fp32, arg [m, c] int32, every element written.  In fp32, with
+ *     v(m, s, ch) = (e ? 0 : f[r, ch]) + (((a[ch,0] * dx + a[ch,1] * dy) + a[ch,2] * dz) + b[ch])
+ *   (the compiler may contract a product and the add that follows it into one fused multiply-add):
+ *     out[m, ch] = max(0, max_s v);  arg[m, ch] = the lowest s attaining the maximum when out > 0, else -1.
+ *   An empty query has v = b[ch] in every slot: out = max(0, b[ch]), arg = 0 when b[ch] > 0.  A NaN v never wins. */
+int spx_voxel_pool_max_fwd(const float *f, const float *xyz, const float *new_xyz, const int32_t *idx,
+                           const uint8_t *empty, const float *a, const float *b, int32_t c, int64_t n_src, int64_t m,
+                           int32_t nsample, float *out, int32_t *arg, spx_stream_t stream);
+
+/* Backward of spx_voxel_pool_max_fwd.  dout [m, c], arg from the forward; g = dout[m, ch] where arg >= 0, else 0.  Any
+ *   output may be NULL (not computed), not all:
+ *   df [n_src, c], fully written (0 where nothing points): df[r, ch] = sum of g over the (m, ch) whose winning slot
+ *     points at r (non-empty queries only), DETERMINISTIC: the (m, s) entries are stable-sorted by r and each run is
+ *     added in ascending m;
+ *   da [c, 3] = sum_m g * d(m, arg), db [c] = sum_m g, DETERMINISTIC: per-block partials over chunks of 128 queries
+ *     (four interleaved ascending sub-sums, added in order), then a fixed-order sum of the partials.
+ *   No gradient flows to xyz or new_xyz.  ws: spx_voxel_pool_max_bwd_ws_bytes bytes. */
+size_t spx_voxel_pool_max_bwd_ws_bytes(int32_t c, int64_t n_src, int64_t m, int32_t nsample);
+int spx_voxel_pool_max_bwd(const float *dout, const int32_t *arg, const int32_t *idx, const uint8_t *empty,
+                           const float *xyz, const float *new_xyz, int32_t c, int64_t n_src, int64_t m, int32_t nsample,
+                           float *df, float *da, float *db, void *ws, size_t ws_bytes, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,11 +4,13 @@ from .point_3dssd import Point3DSSD
 from .pointpillar import PointPillar
 from .second_net import SECONDNet
 from .second_net_iou import SECONDNetIoU
+from .voxel_rcnn import VoxelRCNN
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'SECONDNet': SECONDNet,
     'SECONDNetIoU': SECONDNetIoU,
+    'VoxelRCNN': VoxelRCNN,
     '3DSSD': Point3DSSD,
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,

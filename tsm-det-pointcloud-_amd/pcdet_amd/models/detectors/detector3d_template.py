@@ -290,7 +290,11 @@ class Detector3DTemplate(nn.Module):
             if cfg.NMS_CONFIG.MULTI_CLASSES_NMS:
                 raise NotImplementedError('MULTI_CLASSES_NMS is not used by the SECOND configuration')
             cls_preds, label_preds = torch.max(cls_preds, dim=-1)
-            label_preds = label_preds + 1
+            if batch_dict.get('has_class_labels', False):      # a second stage keeps the first stage's class (reference :281-283)
+                label_key = 'roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels'
+                label_preds = batch_dict[label_key][index]
+            else:
+                label_preds = label_preds + 1
             thresh = cfg.SCORE_THRESH
             if isinstance(thresh, (list, tuple)):   # fork: per-class thresholds + a final cross-class NMS
                 selected, selected_scores = model_nms_utils.multi_thresh(

@@ -242,10 +242,16 @@ class RegLossCenterNet(nn.Module):
         return _reg_loss(pred, target, mask)
 
 
+_CORNER_TEMPLATE = {}
+
+
 def _corners_3d(boxes3d):
     """(N, 7) -> (N, 8, 3) corners in the boxes' own dtype, the reference's boxes_to_corners_3d (box_utils.py:28-53)."""
-    template = boxes3d.new_tensor([[1, 1, -1], [1, -1, -1], [-1, -1, -1], [-1, 1, -1],
-                                   [1, 1, 1], [1, -1, 1], [-1, -1, 1], [-1, 1, 1]]) / 2
+    key = (boxes3d.device, boxes3d.dtype)
+    template = _CORNER_TEMPLATE.get(key)
+    if template is None:      # built once per device and dtype: a host-to-device copy cannot be part of a captured graph
+        template = _CORNER_TEMPLATE[key] = boxes3d.new_tensor([[1, 1, -1], [1, -1, -1], [-1, -1, -1], [-1, 1, -1],
+                                                               [1, 1, 1], [1, -1, 1], [-1, -1, 1], [-1, 1, 1]]) / 2
     corners = boxes3d[:, None, 3:6] * template[None]
     corners = common_utils.rotate_points_along_z(corners, boxes3d[:, 6])
     return corners + boxes3d[:, None, 0:3]

@@ -202,6 +202,12 @@ SIGNATURES = {
     "spx_proposal_sample_ws_bytes": (_sz, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "spx_proposal_sample": (_int, [_vp, _vp, _vp] + [ctypes.c_int32] * 7 + [ctypes.c_float] * 3 +
                             [ctypes.c_double, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_voxel_pool_moments_ws_bytes": (_sz, [_i64, ctypes.c_int32]),
+    "spx_voxel_pool_moments": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp, _sz, _vp]),
+    "spx_voxel_pool_max_fwd": (_int, [_vp] * 7 + [ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp]),
+    "spx_voxel_pool_max_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, _i64, ctypes.c_int32]),
+    "spx_voxel_pool_max_bwd": (_int, [_vp] * 6 + [ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _sz,
+                                                  _vp]),
 }
 
 _lib = None

@@ -2292,3 +2292,102 @@ def proposal_sample(rois, roi_labels, gt_boxes, roi_per_image, fg_per_image, reg
                                   int(bool(by_class)), _ptr(fg_keys), _ptr(slot_u), _ptr(sampled), _ptr(ious),
                                   _ptr(gt_inds), _ptr(ws), wsb, _stream(rois)), "spx_proposal_sample")
     return sampled, ious, gt_inds
+
+
+# ------------------------------------------------------------------------------ voxel-grid max pooling (§27)
+
+def _voxel_pool_args(xyz, new_xyz, idx, empty, what):
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or new_xyz.dim() != 2 or new_xyz.shape[1] != 3 or idx.dim() != 2 \
+            or idx.shape[0] != new_xyz.shape[0] or idx.shape[1] < 1 \
+            or (empty is not None and tuple(empty.shape) != (new_xyz.shape[0],)):
+        raise _lib.SpxError("%s: xyz %s, new_xyz %s, idx %s, empty %s do not match" % (
+            what, tuple(xyz.shape), tuple(new_xyz.shape), tuple(idx.shape), None if empty is None else tuple(empty.shape)))
+    empty = None if empty is None else empty.detach().contiguous().to(torch.uint8)
+    return _f32(xyz), _f32(new_xyz), _i32(idx), empty
+
+
+def voxel_pool_moments(xyz, new_xyz, idx, empty):
+    """spx_voxel_pool_moments: xyz (N, 3), new_xyz (M, 3), idx (M, S) global rows, empty (M) bool / uint8 or None ->
+    float64[9] = (sum d, upper triangle of sum d d^T) of the offsets d = xyz[idx] - new_xyz over all M * S columns, empty
+    queries counting as zero columns (include/spx.h §27).  Fixed summation order; no host read."""
+    _need_gpu(xyz, new_xyz, idx, empty)
+    lib = _lib.load()
+    xyz, new_xyz, idx, empty = _voxel_pool_args(xyz, new_xyz, idx, empty, "voxel_pool_moments")
+    m, s = idx.shape
+    out = torch.empty((9,), dtype=torch.float64, device=xyz.device)
+    wsb = lib.spx_voxel_pool_moments_ws_bytes(m, s)
+    ws = workspace(xyz.device, wsb)
+    check(lib.spx_voxel_pool_moments(_ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(empty), xyz.shape[0], m, s, _ptr(out),
+                                     _ptr(ws), wsb, _stream(xyz)), "spx_voxel_pool_moments")
+    return out
+
+
+def voxel_pool_max_fwd(f, xyz, new_xyz, idx, empty, a, b):
+    """spx_voxel_pool_max_fwd -> out (M, C) fp32, arg (M, C) int32 (the winning slot, -1 where out is 0)."""
+    _need_gpu(f, xyz, new_xyz, idx, empty, a, b)
+    lib = _lib.load()
+    xyz, new_xyz, idx, empty = _voxel_pool_args(xyz, new_xyz, idx, empty, "voxel_pool_max")
+    f, a, b = _f32(f), _f32(a), _f32(b)
+    if f.dim() != 2 or f.shape[0] != xyz.shape[0] or f.shape[1] < 1 or tuple(a.shape) != (f.shape[1], 3) \
+            or tuple(b.shape) != (f.shape[1],):
+        raise _lib.SpxError("voxel_pool_max: f %s, xyz %s, a %s, b %s do not match"
+                            % (tuple(f.shape), tuple(xyz.shape), tuple(a.shape), tuple(b.shape)))
+    m, s = idx.shape
+    n_src, c = f.shape
+    out = torch.empty((m, c), dtype=torch.float32, device=f.device)
+    arg = torch.empty((m, c), dtype=torch.int32, device=f.device)
+    check(lib.spx_voxel_pool_max_fwd(_ptr(f), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(empty), _ptr(a), _ptr(b), c, n_src,
+                                     m, s, _ptr(out), _ptr(arg), _stream(f)), "spx_voxel_pool_max_fwd")
+    return out, arg
+
+
+def voxel_pool_max_bwd(dout, arg, xyz, new_xyz, idx, empty, n_src):
+    """spx_voxel_pool_max_bwd: dout (M, C), arg from the forward -> df (n_src, C), dA (C, 3), db (C), all summed in a
+    fixed order."""
+    _need_gpu(dout, arg, xyz, new_xyz, idx, empty)
+    lib = _lib.load()
+    xyz, new_xyz, idx, empty = _voxel_pool_args(xyz, new_xyz, idx, empty, "voxel_pool_max_bwd")
+    dout, arg = _f32(dout), _i32(arg)
+    m, s = idx.shape
+    if dout.dim() != 2 or dout.shape[0] != m or tuple(arg.shape) != tuple(dout.shape) or int(n_src) != xyz.shape[0]:
+        raise _lib.SpxError("voxel_pool_max_bwd: dout %s, arg %s, idx %s, n_src %d do not match"
+                            % (tuple(dout.shape), tuple(arg.shape), tuple(idx.shape), int(n_src)))
+    c = dout.shape[1]
+    dev = dout.device
+    df = torch.empty((int(n_src), c), dtype=torch.float32, device=dev)
+    da = torch.empty((c, 3), dtype=torch.float32, device=dev)
+    db = torch.empty((c,), dtype=torch.float32, device=dev)
+    wsb = lib.spx_voxel_pool_max_bwd_ws_bytes(c, int(n_src), m, s)
+    ws = workspace(dev, wsb)
+    check(lib.spx_voxel_pool_max_bwd(_ptr(dout), _ptr(arg), _ptr(idx), _ptr(empty), _ptr(xyz), _ptr(new_xyz), c, int(n_src),
+                                     m, s, _ptr(df), _ptr(da), _ptr(db), _ptr(ws), wsb, _stream(dout)),
+          "spx_voxel_pool_max_bwd")
+    return df, da, db
+
+
+class _VoxelPoolMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f, xyz, new_xyz, idx, empty, a, b):
+        out, arg = voxel_pool_max_fwd(f, xyz, new_xyz, idx, empty, a, b)
+        ctx.save_for_backward(arg, xyz, new_xyz, idx, empty)
+        ctx.n_src = f.shape[0]
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        arg, xyz, new_xyz, idx, empty = ctx.saved_tensors
+        df, da, db = voxel_pool_max_bwd(dout, arg, xyz, new_xyz, idx, empty, ctx.n_src)
+        return df, None, None, None, None, da, db
+
+
+def voxel_pool_max(f, xyz, new_xyz, idx, empty, a, b, return_arg=False):
+    """out (M, C) = max(0, max_s f[idx[m, s]] + a . (xyz[idx[m, s]] - new_xyz[m]) + b), the pooling tail of
+    NeighborVoxelSAModuleMSG with its BatchNorm folded into (a, b) (include/spx.h §27).  f (N, C), xyz (N, 3), new_xyz
+    (M, 3), idx (M, S) global rows, empty (M) bool, a (C, 3), b (C).  Differentiable in f, a, b; nothing flows to the
+    coordinates.  return_arg: also the winning slots (M, C) int32."""
+    _need_gpu(f, xyz, new_xyz, idx, empty, a, b)
+    if empty is None:
+        empty = torch.zeros((new_xyz.shape[0],), dtype=torch.bool, device=new_xyz.device)
+    out, arg = _VoxelPoolMax.apply(f, xyz.detach(), new_xyz.detach(), idx, empty, a, b)
+    return (out, arg) if return_arg else out
