@@ -1219,6 +1219,32 @@ int spx_voxel_pool_max_bwd(const float *dout, const int32_t *arg, const int32_t 
                            const float *xyz, const float *new_xyz, int32_t c, int64_t n_src, int64_t m, int32_t nsample,
                            float *df, float *da, float *db, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 28. Two-layer shared-MLP max pooling: the eval-mode tail of a StackSAModuleMSG scale after the ball query
+ *     (csrc/sa_mlp.hip)
+ *    replaces: the two groupings into (M, 3 + C, nsample), Conv2d + eval BatchNorm2d + ReLU twice over
+ *      (1, C, M, nsample) tensors and the max over the slots (reference
+ *      pcdet/ops/pointnet2/pointnet2_stack/pointnet2_modules.py, StackSAModuleMSG with two-layer mlps, max_pool).  The
+ *      first conv's feature columns are the caller's GEMM p = features Wf^T over the SOURCE rows (as in §22); both
+ *      BatchNorms are folded by the caller into (a1, b1), (a2, b2) from their running statistics.  Forward only.
+ *    Queries m in [0, m); slots s in [0, nsample); r = idx[m, s] (GLOBAL rows); e = empty[m] != 0 (empty may be NULL).
+ *    A column is ZERO when e, or when r is outside [0, n_src) (never dereferenced): it has p = 0 and d = 0, so
+ *    h = relu(b1) — the reference zeroes the grouped tensor of an empty ball and still runs the MLP over it; an empty
+ *    query is therefore NOT a zero output row.  idx of an empty query is never read.  Otherwise, in fp32,
+ *      d = xyz[r] - new_xyz[m]
+ *      h[s, c]   = max(0, a1[c] * (p[r, c] + ((wx[c,0] * dx + wx[c,1] * dy) + wx[c,2] * dz)) + b1[c])
+ *      out[m, o] = max_s max(0, a2[o] * (sum_c w2[o, c] * h[s, c]) + b2[o])
+ *    (the compiler may contract a product and the add that follows into one fused multiply-add; the sum over c is a
+ *    chain of fused multiply-adds in the order c = k * c1 / 4 + j, j outer, k inner).
+ *    p [n_src, c1] 16-byte aligned, or NULL (a grouper without features: p = 0); xyz [n_src, 3]; new_xyz [m, 3];
+ *    idx [m, nsample] int32; wx [c1, 3]; a1, b1 [c1]; w2 [c2, c1]; a2, b2 [c2] -> out [m, c2], every element written.
+ *    c1, c2 in {16, 32, 64}, nsample in {16, 32}: anything else SPX_ERR_UNSUPPORTED.  No workspace, no host read, no
+ *    atomics, bitwise reproducible, capturable.  m * nsample, m * c2 >= 2^31 - 1: SPX_ERR_TOO_LARGE.
+ * ---------------------------------------------------------------------------------------------- */
+int spx_sa_mlp2_max(const float *p, const float *xyz, const float *new_xyz, const int32_t *idx, const uint8_t *empty,
+                    const float *wx, const float *a1, const float *b1, const float *w2, const float *a2, const float *b2,
+                    int32_t c1, int32_t c2, int64_t n_src, int64_t m, int32_t nsample, float *out, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
+from .point_head_simple import PointHeadSimple
 from .point_head_template import PointHeadTemplate
 from .point_head_vote_sasa_statistic_distillation import PointHeadVoteSASAStatisticDistillation
 
@@ -9,5 +10,6 @@ __all__ = {
     'AnchorHeadSingle': AnchorHeadSingle,
     'CenterHead': CenterHead,
     'PointHeadTemplate': PointHeadTemplate,
+    'PointHeadSimple': PointHeadSimple,
     'PointHeadVoteSASAStatisticDistillation': PointHeadVoteSASAStatisticDistillation,
 }

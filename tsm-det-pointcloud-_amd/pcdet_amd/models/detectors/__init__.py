@@ -2,6 +2,7 @@ from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .point_3dssd import Point3DSSD
 from .pointpillar import PointPillar
+from .pv_rcnn import PVRCNN
 from .second_net import SECONDNet
 from .second_net_iou import SECONDNetIoU
 from .voxel_rcnn import VoxelRCNN
@@ -11,6 +12,7 @@ __all__ = {
     'SECONDNet': SECONDNet,
     'SECONDNetIoU': SECONDNetIoU,
     'VoxelRCNN': VoxelRCNN,
+    'PVRCNN': PVRCNN,
     '3DSSD': Point3DSSD,
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,

@@ -5,8 +5,9 @@ Differences forced by the fork's drift, all backwards compatible
   * build_backbone_2d keeps `num_bev_features` from the module's own attribute (falls back to the fork's
     num_voxel_neck_features) and never overwrites num_point_features with None;
   * POST_PROCESSING.SCORE_THRESH may be a scalar (upstream) or a per-class list (fork's multi_thresh).
-Only the module slots of the SECOND, SECOND-IoU and 3DSSD paths are populated; the other slots of `module_topology`
-stay None.
+The module slots of the SECOND, SECOND-IoU, Voxel R-CNN, PV-RCNN (pfe: VoxelSetAbstraction, point_head, roi_head) and
+3DSSD paths are populated; `neck` stays None.  A RoI head that reads keypoint features (PVRCNNHead) is refused by name
+when the model has built no PFE.
 """
 import os
 
@@ -16,7 +17,7 @@ import torch.nn as nn
 from ...utils.spconv_utils import find_all_spconv_keys
 from .. import backbones_2d, backbones_3d, dense_heads, roi_heads
 from ..backbones_2d import map_to_bev
-from ..backbones_3d import vfe
+from ..backbones_3d import pfe, vfe
 from ..model_utils import model_nms_utils
 
 
@@ -119,7 +120,19 @@ class Detector3DTemplate(nn.Module):
         return None, model_info_dict
 
     def build_pfe(self, model_info_dict):
-        return self._absent('PFE', model_info_dict)
+        if self.model_cfg.get('PFE', None) is None:
+            return None, model_info_dict
+        name = self.model_cfg.PFE.NAME
+        if name not in pfe.__all__:
+            raise NotImplementedError('PFE %s is not supported (%s)' % (name, ', '.join(pfe.__all__)))
+        m = pfe.__all__[name](
+            model_cfg=self.model_cfg.PFE, voxel_size=model_info_dict['voxel_size'],
+            point_cloud_range=model_info_dict['point_cloud_range'], num_bev_features=model_info_dict['num_bev_features'],
+            num_rawpoint_features=model_info_dict['num_rawpoint_features'])
+        model_info_dict['module_list'].append(m)
+        model_info_dict['num_point_features'] = m.num_point_features
+        model_info_dict['num_point_features_before_fusion'] = m.num_point_features_before_fusion
+        return m, model_info_dict
 
     def build_neck(self, model_info_dict):
         return self._absent('NECK', model_info_dict)
@@ -146,6 +159,9 @@ class Detector3DTemplate(nn.Module):
         if name not in roi_heads.__all__ or name == 'RoIHeadTemplate':
             raise NotImplementedError('ROI_HEAD %s is not supported (second-stage heads: %s)'
                                       % (name, ', '.join(k for k in roi_heads.__all__ if k != 'RoIHeadTemplate')))
+        if name in roi_heads.KEYPOINT_HEADS and getattr(self, 'pfe', None) is None:
+            raise NotImplementedError('ROI_HEAD %s pools keypoint features and MODEL.PFE is missing: the model has no '
+                                      'point-feature encoder (VoxelSetAbstraction) to read them from' % name)
         m = roi_heads.__all__[name](
             model_cfg=self.model_cfg.ROI_HEAD, input_channels=model_info_dict['num_point_features'],
             backbone_channels=model_info_dict.get('backbone_channels', None),

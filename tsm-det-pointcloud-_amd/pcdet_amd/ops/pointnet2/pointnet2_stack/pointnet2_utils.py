@@ -76,13 +76,15 @@ farthest_point_sample = furthest_point_sample = _batch_utils.furthest_point_samp
 
 
 @torch.no_grad()
-def stack_farthest_point_sample(xyz, xyz_batch_cnt, npoint):
+def stack_farthest_point_sample(xyz, xyz_batch_cnt, npoint, total=None):
     """xyz (N1 + N2 ..., 3), counts (batch_size,), npoint an int (per frame), a list or an int tensor (batch_size,) ->
     (sum of npoint,) int32 GLOBAL rows, frame after frame; the first pick of a frame is its first row.  An int or a list
-    costs no host read; a tensor costs the one read of its sum that sizes the output, as in the reference."""
+    costs no host read; a tensor costs the one read of its sum that sizes the output, as in the reference, unless the
+    caller passes that sum as `total` (a device tensor with its sum known on the host: no read, no host-to-device copy,
+    so the call can be captured in a graph)."""
     batch_size = xyz_batch_cnt.shape[0]
     if isinstance(npoint, torch.Tensor):
-        total = int(npoint.sum().item())
+        total = int(npoint.sum().item()) if total is None else int(total)
         npoint = npoint.to(device=xyz.device, dtype=torch.int32)
     else:
         if not isinstance(npoint, (list, tuple)):

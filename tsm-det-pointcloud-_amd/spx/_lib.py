@@ -208,6 +208,7 @@ SIGNATURES = {
     "spx_voxel_pool_max_bwd_ws_bytes": (_sz, [ctypes.c_int32, _i64, _i64, ctypes.c_int32]),
     "spx_voxel_pool_max_bwd": (_int, [_vp] * 6 + [ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _sz,
                                                   _vp]),
+    "spx_sa_mlp2_max": (_int, [_vp] * 11 + [ctypes.c_int32, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp]),
 }
 
 _lib = None

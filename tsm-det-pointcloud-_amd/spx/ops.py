@@ -2391,3 +2391,56 @@ def voxel_pool_max(f, xyz, new_xyz, idx, empty, a, b, return_arg=False):
         empty = torch.zeros((new_xyz.shape[0],), dtype=torch.bool, device=new_xyz.device)
     out, arg = _VoxelPoolMax.apply(f, xyz.detach(), new_xyz.detach(), idx, empty, a, b)
     return (out, arg) if return_arg else out
+
+
+# ------------------------------------------------------------------------------ two-layer SA-MLP max pooling (§28)
+
+SA_MLP2_CHANNELS = (16, 32, 64)
+SA_MLP2_NSAMPLE = (16, 32)
+
+
+def sa_mlp2_supported(c1, c2, nsample):
+    """Whether spx_sa_mlp2_max has a kernel for this shape (PV-RCNN's pointnets)."""
+    return c1 in SA_MLP2_CHANNELS and c2 in SA_MLP2_CHANNELS and nsample in SA_MLP2_NSAMPLE
+
+
+def sa_mlp2_max(P, xyz, new_xyz, idx, empty, Wx, a1, b1, W2, a2, b2):
+    """out (M, C2) = max_s relu(a2 * (W2 h[m, s]) + b2), h[m, s] = relu(a1 * (P[r] + Wx (xyz[r] - new_xyz[m])) + b1),
+    r = idx[m, s]: the eval-mode tail of a two-layer stacked SA pointnet with both BatchNorms folded (include/spx.h §28).
+    P (N, C1) = features @ Wf^T or None, xyz (N, 3), new_xyz (M, 3), idx (M, S) int32 GLOBAL rows, empty (M) bool or
+    None, Wx (C1, 3), a1 / b1 (C1), W2 (C2, C1), a2 / b2 (C2), fp32.  An empty ball, and a row of idx outside [0, N), is a
+    zero column (h = relu(b1)), not a zero output.  Forward only: tensors that require grad are refused.  C1, C2 in
+    {16, 32, 64} and S in {16, 32}; anything else raises SpxError.  No host read; capturable; bitwise reproducible."""
+    named = (("P", P), ("xyz", xyz), ("new_xyz", new_xyz), ("idx", idx), ("empty", empty), ("Wx", Wx), ("a1", a1),
+             ("b1", b1), ("W2", W2), ("a2", a2), ("b2", b2))
+    _need_gpu(*[t for _, t in named])
+    for name, t in named:
+        if t is not None and t.requires_grad:
+            raise _lib.SpxError("sa_mlp2_max: %s requires grad; the op is forward only (detach it, or use the "
+                                "composition to train)" % name)
+    for name, t in named:
+        if t is not None and name not in ("idx", "empty") and t.dtype != torch.float32:
+            raise _lib.SpxError("sa_mlp2_max: %s is %s; the op is fp32 in and out" % (name, t.dtype))
+    lib = _lib.load()
+    xyz, new_xyz, idx, empty = _voxel_pool_args(xyz, new_xyz, idx, empty, "sa_mlp2_max")
+    Wx, a1, b1, W2, a2, b2 = _f32(Wx), _f32(a1), _f32(b1), _f32(W2), _f32(a2), _f32(b2)
+    m, s = idx.shape
+    n_src = xyz.shape[0]
+    c2, c1 = (W2.shape if W2.dim() == 2 else (0, 0))
+    if not sa_mlp2_supported(c1, c2, s):
+        raise _lib.SpxError("sa_mlp2_max: unsupported shape C1 = %d, C2 = %d, S = %d; C1 and C2 must be in %s and S in %s"
+                            % (c1, c2, s, SA_MLP2_CHANNELS, SA_MLP2_NSAMPLE))
+    if tuple(Wx.shape) != (c1, 3) or tuple(a1.shape) != (c1,) or tuple(b1.shape) != (c1,) or tuple(a2.shape) != (c2,) \
+            or tuple(b2.shape) != (c2,) or (P is not None and tuple(P.shape) != (n_src, c1)):
+        raise _lib.SpxError("sa_mlp2_max: P %s, xyz %s, Wx %s, a1 %s, b1 %s, W2 %s, a2 %s, b2 %s do not match" % (
+            None if P is None else tuple(P.shape), tuple(xyz.shape), tuple(Wx.shape), tuple(a1.shape), tuple(b1.shape),
+            tuple(W2.shape), tuple(a2.shape), tuple(b2.shape)))
+    if P is not None:
+        P = _f32(P)
+        if P.data_ptr() % 16:
+            P = P.clone()
+    out = torch.empty((m, c2), dtype=torch.float32, device=xyz.device)
+    check(lib.spx_sa_mlp2_max(_ptr(P), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(empty), _ptr(Wx), _ptr(a1), _ptr(b1),
+                              _ptr(W2), _ptr(a2), _ptr(b2), c1, c2, n_src, m, s, _ptr(out), _stream(xyz)),
+          "spx_sa_mlp2_max")
+    return out
