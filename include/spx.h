@@ -1245,6 +1245,50 @@ int spx_sa_mlp2_max(const float *p, const float *xyz, const float *new_xyz, cons
                     const float *wx, const float *a1, const float *b1, const float *w2, const float *a2, const float *b2,
                     int32_t c1, int32_t c2, int64_t n_src, int64_t m, int32_t nsample, float *out, spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 29. Post-processing of dense (B, N, .) predictions without a host read (csrc/dense_post_process.hip)
+ *    replaces: the per-frame mask / nonzero / topk / NMS / count read of Detector3DTemplate.post_processing over the
+ *      anchors of AnchorHeadSingle and over the RoIs of a second stage (reference detector3d_template.py:207-349,
+ *      model_nms_utils.py), and the topk + per-frame NMS of RoIHeadTemplate.proposal_layer (roi_head_template.py:45-95).
+ *    §15 keeps a frame's candidates in one workgroup's LDS (n <= 4096); here n is any size with b * n < 2^31: an exact
+ *    radix select over all rows, one LDS sort per (frame, class), the NMS pair tests spread over the whole grid.
+ *    Every stage is a launch of its own; the launch count depends on the arguments only; integer atomics only; no host
+ *    read; bitwise reproducible; capturable.  frame f owns the rows [f * n, (f + 1) * n).
+ * ---------------------------------------------------------------------------------------------- */
+
+size_t spx_dense_select_ws_bytes(int32_t b, int64_t n, int32_t n_thresh, int64_t pre_max);
+
+/* The pre_max best members of every (frame, class).  scores [b * n] (already normalised), labels [b * n] int32 (1-based,
+ *   read only when per_class != 0), thresholds: HOST float[n_thresh], or NULL for no threshold.
+ *   Members of (frame f, class c): rows of f with score >= thresholds[c] (NULL: every row) and, per_class != 0,
+ *   label == c + 1; per_class == 0 needs n_thresh == 1.  A NaN score is NEVER a member (torch.topk ranks it first).
+ *   -> cand [b, n_thresh, pre_max] int64: the members by score descending, EQUAL SCORES LOWER ROW FIRST (-0 equals +0),
+ *      the first pre_max, as rows in [0, b * n), -1 past the count; cand_count [b, n_thresh] int32.  Every element
+ *      written on every call.  Exact for any score distribution.
+ *   1 <= pre_max <= 16384, b <= 65535, b * n < 2^31, else SPX_ERR_TOO_LARGE; n_thresh <= 8 else SPX_ERR_UNSUPPORTED;
+ *   b * n == 0: SPX_OK, nothing launched.  Launches: 1 + 2 * ceil((32 + bits(n - 1)) / 11) + 2. */
+int spx_dense_select(const float *scores, const int32_t *labels, int32_t b, int64_t n, const float *thresholds,
+                     int32_t n_thresh, int64_t pre_max, int per_class, int64_t *cand, int32_t *cand_count, void *ws,
+                     size_t ws_bytes, spx_stream_t stream);
+
+size_t spx_dense_post_process_ws_bytes(int32_t b, int64_t n, int32_t n_thresh, int64_t pre_max, int64_t post_max);
+
+/* spx_dense_select, then per (frame, class) the greedy NMS of §15 over the sorted candidates (the pair test of
+ *   csrc/box_iou.h, (earlier, later); rotated BEV, or axis aligned when axis_aligned != 0) cut at post_max, then with
+ *   per_class != 0 the classes' survivors ordered again and reduced by one more NMS: the semantics and the OUTPUTS of
+ *   spx_point_post_process (sel, count, out_boxes, out_scores, out_labels with K = spx_point_post_process_capacity(n,
+ *   n_thresh, post_max, per_class) rows per frame, every element written), for any n, plus the NULL threshold.
+ *   boxes [b * n, box_ld] fp32, box_ld >= 7, the first 7 columns are the box.
+ *   The pair tests fill the upper triangle of a bit matrix [min(pre_max, n), ceil(min(pre_max, n) / 64)] of 64-bit words
+ *   per (frame, class) in the workspace; the greedy walk stops at post_max kept boxes.
+ *   Limits of spx_dense_select, and n_thresh * min(post_max, pre_max, n) <= 4096 (the final stage is one workgroup per
+ *   frame) else SPX_ERR_TOO_LARGE.  Three launches after the selection's. */
+int spx_dense_post_process(const float *scores, const int32_t *labels, const float *boxes, int32_t box_ld, int32_t b,
+                           int64_t n, const float *thresholds, int32_t n_thresh, float nms_thresh, int64_t pre_max,
+                           int64_t post_max, int axis_aligned, int per_class, int64_t *sel, int32_t *count,
+                           float *out_boxes, float *out_scores, int64_t *out_labels, void *ws, size_t ws_bytes,
+                           spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

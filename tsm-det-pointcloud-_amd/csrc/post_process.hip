@@ -15,154 +15,9 @@
 // boxes still alive is taken by ballots (one wave per row), every thread resolves the chunk's greedy order from the 64
 // row masks, and each later live box is then tested against the chunk's kept boxes until the first one suppresses it.
 // The pair test is box_iou.h's, with (earlier, later) argument order, as in nms.hip.
-#include "box_iou.h"
+#include "post_nms.h"
 
 namespace {
-
-constexpr int kMaxN = 4096;       // candidates per frame: the keys of one frame fit a 32 KiB LDS array
-constexpr int kThreads = 1024;
-constexpr int kMaxThresh = 8;
-
-struct Thresh {
-  float v[kMaxThresh];
-};
-
-struct NmsLds {
-  unsigned long long keys[kMaxN];
-  unsigned long long remv[64];    // bit j of word w: sorted position 64 w + j is suppressed (or, past a chunk, not kept)
-  unsigned long long diag[64];
-  float cbox[64 * 7];
-  int wpre[65];
-  int cnt;
-};
-
-// float -> uint32 whose unsigned order is the float order (-0 counts as +0, as in a float comparison)
-__device__ __forceinline__ uint32_t ordered_bits(float s) {
-  uint32_t u = __float_as_uint(s + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// key of a member row: never 0, so 0 pads the sort
-__device__ __forceinline__ unsigned long long make_key(float score, int row) {
-  return ((unsigned long long)ordered_bits(score) << 32) | (unsigned long long)(~(uint32_t)row);
-}
-
-__device__ __forceinline__ int row_of(unsigned long long key) { return (int)(~(uint32_t)key); }
-
-__device__ __forceinline__ int pow2_at_least(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-// bitonic sort of keys[0, p), descending; p a power of two; called by the whole workgroup after a barrier
-__device__ void sort_desc(unsigned long long* keys, int p) {
-  for (int k = 2; k <= p; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < p; i += blockDim.x) {
-        const int x = i ^ j;
-        if (x > i) {
-          const unsigned long long a = keys[i], b = keys[x];
-          const bool desc = (i & k) == 0;
-          if (desc ? a < b : a > b) {
-            keys[i] = b;
-            keys[x] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
-
-template <bool NORMAL>
-__device__ __forceinline__ bool suppresses(const float* earlier, const float* later, float thresh) {
-  const float v = NORMAL ? iou_normal(earlier, later) : iou_bev(earlier, later);
-  return v > thresh;
-}
-
-// Greedy NMS over the sorted positions [0, m) of s.keys (rows of the frame whose boxes start at fb).  On return
-// (after a barrier) bit j of ~s.remv[w] says that position 64 w + j is kept (bits at or past m in the last word are set
-// too: mask them).
-template <bool NORMAL>
-__device__ void greedy_nms(const float* __restrict__ fb, NmsLds& s, int m, float thresh) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nw = blockDim.x >> 6;
-  for (int w = t; w < 64; w += blockDim.x) s.remv[w] = 0ull;
-  __syncthreads();
-  const int nchunks = (m + 63) >> 6;
-  for (int c = 0; c < nchunks; ++c) {
-    const int base = c << 6;
-    const int size = min(64, m - base);
-    unsigned long long alive = ~s.remv[c];
-    if (size < 64) alive &= (1ull << size) - 1ull;
-    for (int e = t; e < size * 7; e += blockDim.x)
-      s.cbox[e] = fb[(int64_t)row_of(s.keys[base + e / 7]) * 7 + e % 7];
-    __syncthreads();
-    // the chunk's own tile: row i (one wave each), column = lane; only pairs of live boxes
-    for (int i = wave; i < size; i += nw) {
-      bool hit = false;
-      if (lane > i && lane < size && ((alive >> i) & 1ull) && ((alive >> lane) & 1ull))
-        hit = suppresses<NORMAL>(s.cbox + i * 7, s.cbox + lane * 7, thresh);
-      const unsigned long long row_mask = __ballot(hit);
-      if (lane == 0) s.diag[i] = row_mask;
-    }
-    __syncthreads();
-    unsigned long long kept = 0ull;      // the same in every thread
-    for (int i = 0; i < size; ++i)
-      if ((alive >> i) & 1ull) {
-        kept |= 1ull << i;
-        alive &= ~s.diag[i];
-      }
-    if (t == 0) s.remv[c] = ~kept;
-    // later boxes against the chunk's kept ones; a wave owns 64 consecutive positions = one word of remv
-    for (int jb = base + 64 + (wave << 6); jb < m; jb += blockDim.x) {
-      const int j = jb + lane;
-      bool hit = false;
-      if (j < m && !((s.remv[jb >> 6] >> lane) & 1ull)) {
-        float me[7];
-        const float* src = fb + (int64_t)row_of(s.keys[j]) * 7;
-#pragma unroll
-        for (int q = 0; q < 7; ++q) me[q] = src[q];
-        unsigned long long kk = kept;
-        while (kk) {
-          const int i = __ffsll(kk) - 1;
-          kk &= kk - 1ull;
-          if (suppresses<NORMAL>(s.cbox + i * 7, me, thresh)) {
-            hit = true;
-            break;
-          }
-        }
-      }
-      const unsigned long long word = __ballot(hit);
-      if (lane == 0 && word) s.remv[jb >> 6] |= word;
-    }
-    __syncthreads();
-  }
-}
-
-// ranks of the kept positions: s.wpre[w] = kept positions before word w; returns the total (after a barrier)
-__device__ int kept_prefix(NmsLds& s, int m) {
-  const int nchunks = (m + 63) >> 6;
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int w = 0; w < nchunks; ++w) {
-      s.wpre[w] = acc;
-      unsigned long long k = ~s.remv[w];
-      const int size = min(64, m - (w << 6));
-      if (size < 64) k &= (1ull << size) - 1ull;
-      acc += __popcll(k);
-    }
-    s.wpre[nchunks] = acc;
-  }
-  __syncthreads();
-  return s.wpre[nchunks];
-}
-
-// rank of kept position j among the kept ones, or -1
-__device__ __forceinline__ int kept_rank(const NmsLds& s, int j) {
-  const unsigned long long k = ~s.remv[j >> 6];
-  if (!((k >> (j & 63)) & 1ull)) return -1;
-  return s.wpre[j >> 6] + __popcll(k & ((1ull << (j & 63)) - 1ull));
-}
 
 // grid (b, n_thresh): members of one class of one frame -> up to post_cap survivor keys in score order
 template <bool NORMAL>
@@ -191,76 +46,13 @@ __global__ __launch_bounds__(kThreads) void k_class_nms(const float* __restrict_
   __syncthreads();
   sort_desc(s.keys, p);
   const int m = min(cnt, pre_max);
-  greedy_nms<NORMAL>(boxes + row0 * 7, s, m, nms_thresh);
+  greedy_nms<NORMAL>(boxes + row0 * 7, 7, s, m, nms_thresh);
   const int total = kept_prefix(s, m);
   for (int j = t; j < m; j += blockDim.x) {
     const int rank = kept_rank(s, j);
     if (rank >= 0 && rank < post_cap) surv[(int64_t)slot * post_cap + rank] = s.keys[j];
   }
   if (t == 0) scnt[slot] = min(total, post_cap);
-}
-
-// grid (b): the classes' survivors -> final order, one more NMS (final_nms) -> the padded outputs
-template <bool NORMAL>
-__global__ __launch_bounds__(kThreads) void k_frame_out(const float* __restrict__ scores, const int32_t* __restrict__ labels,
-                                                        const float* __restrict__ boxes, int n, int n_thresh,
-                                                        float nms_thresh, int post_cap, int final_nms,
-                                                        const unsigned long long* __restrict__ surv,
-                                                        const int32_t* __restrict__ scnt, int cap, int64_t* __restrict__ sel,
-                                                        int32_t* __restrict__ count, float* __restrict__ out_boxes,
-                                                        float* __restrict__ out_scores, int64_t* __restrict__ out_labels) {
-  __shared__ NmsLds s;
-  __shared__ int coff[kMaxThresh + 1];
-  const int t = threadIdx.x, b = blockIdx.x;
-  const int64_t row0 = (int64_t)b * n;
-  if (t == 0) {
-    int acc = 0;
-    for (int c = 0; c < n_thresh; ++c) {
-      coff[c] = acc;
-      acc += scnt[b * n_thresh + c];
-    }
-    coff[n_thresh] = acc;
-  }
-  __syncthreads();
-  const int m = min(coff[n_thresh], kMaxN);   // <= n: the classes' rows are disjoint
-  for (int c = 0; c < n_thresh; ++c) {
-    const int len = coff[c + 1] - coff[c];
-    for (int i = t; i < len && coff[c] + i < m; i += blockDim.x)
-      s.keys[coff[c] + i] = surv[(int64_t)(b * n_thresh + c) * post_cap + i];
-  }
-  int total = 0;
-  if (m > 0) {
-    if (final_nms) {
-      const int p = pow2_at_least(m);
-      for (int i = m + t; i < p; i += blockDim.x) s.keys[i] = 0ull;
-      __syncthreads();
-      sort_desc(s.keys, p);
-      greedy_nms<NORMAL>(boxes + row0 * 7, s, m, nms_thresh);
-    } else {
-      for (int w = t; w < 64; w += blockDim.x) s.remv[w] = 0ull;
-      __syncthreads();
-    }
-    total = min(kept_prefix(s, m), cap);
-    for (int j = t; j < m; j += blockDim.x) {
-      const int rank = kept_rank(s, j);
-      if (rank < 0 || rank >= cap) continue;
-      const int64_t row = row0 + row_of(s.keys[j]), o = (int64_t)b * cap + rank;
-      sel[o] = row;
-#pragma unroll
-      for (int q = 0; q < 7; ++q) out_boxes[o * 7 + q] = boxes[row * 7 + q];
-      out_scores[o] = scores[row];
-      out_labels[o] = (int64_t)labels[row];
-    }
-  }
-  for (int r = total + t; r < cap; r += blockDim.x) {
-    const int64_t o = (int64_t)b * cap + r;
-    sel[o] = -1;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) out_boxes[o * 7 + q] = 0.f;
-    out_scores[o] = 0.f;
-    out_labels[o] = 0;
-  }
-  if (t == 0) count[b] = total;
 }
 
 // 3-D IoU with the roundings of iou3d_nms_utils.boxes_iou3d_gpu (every product and sum rounded on its own, as the
@@ -369,12 +161,12 @@ extern "C" int spx_point_post_process(const float* scores, const int32_t* labels
   if (axis_aligned) {
     hipLaunchKernelGGL((k_class_nms<true>), g1, blk, 0, s, scores, labels, boxes, (int)n, th, pc, nms_thresh, pre, post_cap,
                        surv, scnt);
-    hipLaunchKernelGGL((k_frame_out<true>), g2, blk, 0, s, scores, labels, boxes, (int)n, (int)n_thresh, nms_thresh,
+    hipLaunchKernelGGL((k_frame_out<true>), g2, blk, 0, s, scores, labels, boxes, 7, (int)n, (int)n_thresh, nms_thresh,
                        post_cap, pc, surv, scnt, cap, sel, count, out_boxes, out_scores, out_labels);
   } else {
     hipLaunchKernelGGL((k_class_nms<false>), g1, blk, 0, s, scores, labels, boxes, (int)n, th, pc, nms_thresh, pre, post_cap,
                        surv, scnt);
-    hipLaunchKernelGGL((k_frame_out<false>), g2, blk, 0, s, scores, labels, boxes, (int)n, (int)n_thresh, nms_thresh,
+    hipLaunchKernelGGL((k_frame_out<false>), g2, blk, 0, s, scores, labels, boxes, 7, (int)n, (int)n_thresh, nms_thresh,
                        post_cap, pc, surv, scnt, cap, sel, count, out_boxes, out_scores, out_labels);
   }
   SPX_CHECK_LAUNCH();

@@ -49,6 +49,7 @@ class PillarVFE(VFETemplate):
         self.with_distance = self.model_cfg.WITH_DISTANCE
         self.use_absolute_xyz = self.model_cfg.USE_ABSLOTE_XYZ
         self.num_raw_features = int(num_point_features)
+        self.num_point_features = self.num_raw_features      # columns of a point after the frame index, as in MeanVFE
         num_point_features += 6 if self.use_absolute_xyz else 3
         if self.with_distance:
             num_point_features += 1

@@ -181,16 +181,51 @@ class Detector3DTemplate(nn.Module):
     # frames, ~1 500 kept boxes each) -- profiles/post_process_bench.log.  Nothing in between was measured.
     FUSED_DEFAULT_MAX_N = 512
 
-    def _fused_post_plan(self, batch_dict):
+    def _dense_post_plan(self, batch_dict):
+        """_fused_post_plan for dense (B, N, .) predictions of an anchor head or a second stage (no batch_index), served by
+        spx.ops.dense_post_process: any N, NMS_PRE_MAXSIZE up to ops.DENSE_POST_PROCESS_MAX_PRE, at most
+        ops.POST_PROCESS_MAX_N kept boxes per frame over the classes."""
+        from spx import ops
+        cfg = self.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        boxes, cls = batch_dict.get('batch_box_preds', None), batch_dict.get('batch_cls_preds', None)
+        batch_size = int(batch_dict['batch_size'])
+        if not isinstance(boxes, torch.Tensor) or not isinstance(cls, torch.Tensor) or not boxes.is_cuda:
+            return None
+        if boxes.dim() != 3 or cls.dim() != 3 or cls.shape[-1] not in (1, self.num_class) or boxes.shape[-1] < 7:
+            return None
+        if nms.MULTI_CLASSES_NMS or nms.NMS_TYPE not in self._FUSED_NMS_TYPES:
+            return None
+        n = boxes.shape[1]
+        if batch_size < 1 or n == 0 or boxes.shape[0] != batch_size or tuple(cls.shape[:2]) != (batch_size, n):
+            return None
+        thresh = cfg.SCORE_THRESH
+        per_class = isinstance(thresh, (list, tuple))
+        thresh = [float(t) for t in thresh] if per_class else [float(thresh)]
+        if not isinstance(nms.NMS_PRE_MAXSIZE, int) or not isinstance(nms.NMS_POST_MAXSIZE, int):
+            return None
+        pre_max, post_max = int(nms.NMS_PRE_MAXSIZE), int(nms.NMS_POST_MAXSIZE)
+        if not 1 <= len(thresh) <= 8 or not 1 <= pre_max <= ops.DENSE_POST_PROCESS_MAX_PRE or post_max < 1 \
+                or len(thresh) * min(post_max, pre_max, n) > ops.POST_PROCESS_MAX_N:
+            return None
+        return dict(batch_size=batch_size, n=n, thresholds=thresh, per_class=per_class, nms_thresh=float(nms.NMS_THRESH),
+                    pre_max=pre_max, post_max=post_max, axis_aligned=self._FUSED_NMS_TYPES[nms.NMS_TYPE], dense=True)
+
+    def _fused_post_plan(self, batch_dict, dense=None):
         """The settings of the fused post-processing (spx.ops.point_post_process) for this batch, or None where it does
         not apply: flat point-head predictions with batch_index, a row count that divides into batch_size frames of at
         most ops.POST_PROCESS_MAX_N candidates, NMS_TYPE nms_gpu / nms_normal_gpu, no MULTI_CLASSES_NMS.  Host values
         only, no device read; that the frames really are contiguous and equally long is the device flag layout_ok of
-        post_processing_static."""
+        post_processing_static.
+        Dense (B, N, .) predictions without batch_index (_dense_post_plan) give a plan only when asked for: dense=True, or
+        dense=None and POST_PROCESSING.FUSED is True."""
         from spx import ops
         cfg = self.model_cfg.POST_PROCESSING
         nms = cfg.NMS_CONFIG
         index, boxes, cls = (batch_dict.get(k, None) for k in ('batch_index', 'batch_box_preds', 'batch_cls_preds'))
+        if index is None and isinstance(boxes, torch.Tensor) and boxes.dim() == 3:
+            want = cfg.get('FUSED', None) is True if dense is None else bool(dense)
+            return self._dense_post_plan(batch_dict) if want else None
         batch_size = int(batch_dict['batch_size'])
         if not all(isinstance(t, torch.Tensor) for t in (index, boxes, cls)):
             return None
@@ -218,20 +253,36 @@ class Detector3DTemplate(nn.Module):
           pred_labels (B, K) int64 (zeros past count); layout_ok: 0-dim bool, False when batch_index is not B equal,
           contiguous frames (the results are then meaningless); with gt_boxes and RECALL_THRESH_LIST also recalled
           (B, T) int32 and num_gt (B) int32 (spx.ops.recall_count).
+        Dense (B, N, .) predictions (a plan of _dense_post_plan) go through spx.ops.dense_post_process: sel then counts
+        rows of the flattened (B * N, .) predictions, the labels are roi_labels / batch_pred_labels when has_class_labels
+        is set, and layout_ok is constantly True.
         Raises where the fused path does not apply (_fused_post_plan)."""
         from spx import ops
         plan = plan or self._fused_post_plan(batch_dict)
         if plan is None:
             raise NotImplementedError('post_processing_static needs flat point-head predictions of equal frames of at '
-                                      'most %d candidates and NMS_TYPE nms_gpu / nms_normal_gpu' % ops.POST_PROCESS_MAX_N)
+                                      'most %d candidates, or dense (B, N, .) predictions with POST_PROCESSING.FUSED: '
+                                      'True, and NMS_TYPE nms_gpu / nms_normal_gpu' % ops.POST_PROCESS_MAX_N)
         cfg = self.model_cfg.POST_PROCESSING
         b, n = plan['batch_size'], plan['n']
+        dense = plan.get('dense', False)
         box_preds, src_cls_preds = batch_dict['batch_box_preds'], batch_dict['batch_cls_preds']
         cls_preds = src_cls_preds if batch_dict['cls_preds_normalized'] else torch.sigmoid(src_cls_preds)
         scores, labels = torch.max(cls_preds, dim=-1)
-        res = ops.point_post_process(scores, labels + 1, box_preds, b, plan['thresholds'], plan['nms_thresh'],
-                                     plan['pre_max'], plan['post_max'], axis_aligned=plan['axis_aligned'],
-                                     per_class=plan['per_class'])
+        if dense:
+            if batch_dict.get('has_class_labels', False):   # a second stage keeps the first stage's class
+                labels = batch_dict['roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels']
+            else:
+                labels = labels + 1
+            box_preds = box_preds.reshape(b * n, box_preds.shape[-1])
+            src_cls_preds = src_cls_preds.reshape(b * n, src_cls_preds.shape[-1])
+            res = ops.dense_post_process(scores.reshape(-1), labels.reshape(-1), box_preds, b, plan['thresholds'],
+                                         plan['nms_thresh'], plan['pre_max'], plan['post_max'],
+                                         axis_aligned=plan['axis_aligned'], per_class=plan['per_class'])
+        else:
+            res = ops.point_post_process(scores, labels + 1, box_preds, b, plan['thresholds'], plan['nms_thresh'],
+                                         plan['pre_max'], plan['post_max'], axis_aligned=plan['axis_aligned'],
+                                         per_class=plan['per_class'])
         out = {'sel': res['sel'], 'count': res['count'], 'pred_boxes': res['boxes'], 'pred_scores': res['scores'],
                'pred_labels': res['labels']}
         if box_preds.shape[1] != 7 or box_preds.dtype != torch.float32:     # keep the caller's columns and dtype
@@ -240,8 +291,11 @@ class Detector3DTemplate(nn.Module):
         if cfg.get('OUTPUT_RAW_SCORE', False):
             raw = torch.max(src_cls_preds, dim=-1)[0]
             out['pred_scores'] = raw[res['sel'].clamp_min(0)] * (res['sel'] >= 0).to(raw.dtype)
-        frame = torch.arange(b, device=box_preds.device, dtype=batch_dict['batch_index'].dtype).view(b, 1)
-        out['layout_ok'] = (batch_dict['batch_index'].reshape(b, n) == frame).all()
+        if dense:
+            out['layout_ok'] = torch.ones((), dtype=torch.bool, device=box_preds.device)
+        else:
+            frame = torch.arange(b, device=box_preds.device, dtype=batch_dict['batch_index'].dtype).view(b, 1)
+            out['layout_ok'] = (batch_dict['batch_index'].reshape(b, n) == frame).all()
         thresh_list = cfg.get('RECALL_THRESH_LIST', None)
         if batch_dict.get('gt_boxes', None) is not None and thresh_list:
             out['recalled'], out['num_gt'] = ops.recall_count(res['boxes'], res['count'], batch_dict['gt_boxes'],

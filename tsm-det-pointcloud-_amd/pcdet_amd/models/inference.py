@@ -176,6 +176,57 @@ class GraphedCenterPoint(GraphedDetector):
         return self.pred_dicts()
 
 
+class GraphedAnchorDetector(GraphedDetector):
+    """Eval forward of an anchor-head detector (SECOND, PointPillars) WITH its score threshold, top-K and NMS as ONE
+    hipGraph replay.
+
+    Same static point buffer, padding row, row capacities, warm-up and capture as GraphedDetector; the forward ends in
+    Detector3DTemplate.post_processing_static, which serves the dense (B, anchors, .) predictions through
+    spx.ops.dense_post_process (no host read) whatever POST_PROCESSING.FUSED says.  That the capture succeeds is itself
+    the check that no host read is left on the path.  Without gt_boxes there is no recall record."""
+
+    def _forward(self):
+        """The eager static path: what the graph holds.  Returns post_processing_static's dict, the head's dense
+        predictions it read and the live row counts of every capacity the modules report."""
+        bd = {'points': self.points, 'batch_size': self.batch_size, 'static_caps': self.static_caps}
+        with torch.no_grad():
+            for m in self.modules:
+                bd = m(bd)
+            plan = self.model._fused_post_plan(bd, dense=True)
+            if plan is None:
+                raise NotImplementedError('GraphedAnchorDetector needs dense (B, N, .) predictions that '
+                                          'Detector3DTemplate._dense_post_plan admits')
+            out = dict(self.model.post_processing_static(bd, plan))
+        out.update({k: bd[k] for k in ('batch_cls_preds', 'batch_box_preds', 'cls_preds_normalized')})
+        out['batch_size'] = self.batch_size
+        out['counts'] = {'voxels': bd['voxel_num_valid']}
+        ms = bd.get('multi_scale_3d_features', None)
+        if ms is not None:
+            out['counts'].update({'spconv2': ms['x_conv2'].n_valid, 'spconv3': ms['x_conv3'].n_valid,
+                                  'spconv4': ms['x_conv4'].n_valid,
+                                  'spconv_down2': bd['encoded_spconv_tensor'].n_valid})
+        return out
+
+    def pred_dicts(self):
+        """The last call's result as model.post_processing returns it: (pred_dicts, recall_dict).  One host read (the
+        frames' counts and the live row counts); raises if a row capacity overflowed, the results are then those of a
+        truncated scene."""
+        st = self.out
+        b = self.batch_size
+        keys = sorted(st['counts'])
+        host = torch.cat([st['count'].to(torch.int64)] + [st['counts'][k].reshape(-1)[:1].to(torch.int64) for k in keys]).tolist()
+        caps = dict(self.static_caps, voxels=self.vox_cap)
+        bad = {k: (v, caps[k]) for k, v in zip(keys, host[b:]) if v > caps[k]}
+        if bad:
+            raise RuntimeError("GraphedAnchorDetector: row capacities exceeded (live rows, capacity): %s" % bad)
+        preds = [{'pred_boxes': st['pred_boxes'][i, :host[i]], 'pred_scores': st['pred_scores'][i, :host[i]],
+                  'pred_labels': st['pred_labels'][i, :host[i]]} for i in range(b)]
+        return preds, {}
+
+    def post_process(self):
+        return self.pred_dicts()
+
+
 class GraphedPointDetector(object):
     """Eval forward of a point detector (Point3DSSD: VoxelPointNet2FSMSGDistillation backbone, vote head) with its
     post-processing as ONE hipGraph replay.

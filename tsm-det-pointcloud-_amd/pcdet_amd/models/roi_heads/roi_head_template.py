@@ -4,6 +4,7 @@ the proposal layer, target assignment with the canonical transform, the box / cl
 Differences from the reference, all so that a training step needs no host read and captures under torch.cuda.graph:
   * proposal_layer takes one batched torch.topk, one spx.ops.nms_bev per frame and a masked gather of the first
     NMS_POST_MAXSIZE kept positions against the device-side count; the reference reads the kept count back per frame.
+    With NMS_CONFIG.FUSED: True one spx.ops.dense_post_process call replaces the topk and the per-frame loop.
   * proposal scores: the fork multiplies sigmoid(max class logit) by sigmoid(batch_dict['candidate_score']), a key only
     its own neck writes.  That score is used when the key is present; without it the score is upstream OpenPCDet's raw
     maximum class logit.
@@ -75,6 +76,9 @@ class RoIHeadTemplate(nn.Module):
         if candidate is not None:
             scores = torch.sigmoid(scores) * torch.sigmoid(candidate.reshape(batch_size, n))
         k = min(int(nms_config.NMS_PRE_MAXSIZE), n)
+        if nms_config.get('FUSED', False) and batch_size * n > 0:
+            return self._proposal_layer_fused(batch_dict, nms_config, box_preds, scores, labels, k, post,
+                                              cls_preds.shape[-1] > 1)
         top_scores, order = torch.topk(scores, k=k, dim=1)
         top_boxes = torch.gather(box_preds, 1, order.unsqueeze(-1).expand(-1, -1, box_preds.shape[-1]))
         top_labels = torch.gather(labels, 1, order)
@@ -94,6 +98,30 @@ class RoIHeadTemplate(nn.Module):
         batch_dict['roi_scores'] = roi_scores
         batch_dict['roi_labels'] = roi_labels + 1
         batch_dict['has_class_labels'] = True if cls_preds.shape[-1] > 1 else False
+        batch_dict.pop('batch_index', None)
+        return batch_dict
+
+    def _proposal_layer_fused(self, batch_dict, nms_config, box_preds, scores, labels, pre, post, has_class_labels):
+        """NMS_CONFIG.FUSED: the selection, the NMS and the cut of every frame in one spx.ops.dense_post_process call
+        (class agnostic, no threshold), then the gathers.  Same outputs as the loop above for scores without NaN (the op
+        never selects a NaN, torch.topk ranks it first) and without ties at the cut (torch.topk's order of equal scores is
+        unspecified; the op takes the lower row)."""
+        from spx import ops
+        batch_size, n = scores.shape
+        flat_boxes = box_preds.reshape(batch_size * n, box_preds.shape[-1])
+        flat_scores, flat_labels = scores.reshape(-1), labels.reshape(-1)
+        res = ops.dense_post_process(flat_scores, flat_labels + 1, flat_boxes, batch_size, None, nms_config.NMS_THRESH,
+                                     pre, post, axis_aligned=_AXIS_ALIGNED[nms_config.NMS_TYPE], per_class=False)
+        sel = F.pad(res['sel'], (0, post - res['sel'].shape[1]), value=-1)         # (B, P); K = min(n, P) columns come back
+        valid = sel >= 0
+        # positions past the count read the frame's best row, as the loop's keep = 0 does, and are zeroed the same way
+        # (a frame that selected nothing, all scores NaN, reads its own first row)
+        first = torch.arange(batch_size, device=sel.device, dtype=sel.dtype).view(-1, 1) * n
+        sel = torch.where(valid, sel, torch.where(valid[:, :1], sel[:, :1], first))
+        batch_dict['rois'] = flat_boxes[sel] * valid.unsqueeze(-1)
+        batch_dict['roi_scores'] = flat_scores[sel] * valid
+        batch_dict['roi_labels'] = flat_labels[sel] * valid + 1
+        batch_dict['has_class_labels'] = has_class_labels
         batch_dict.pop('batch_index', None)
         return batch_dict
 

@@ -209,6 +209,12 @@ SIGNATURES = {
     "spx_voxel_pool_max_bwd": (_int, [_vp] * 6 + [ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _sz,
                                                   _vp]),
     "spx_sa_mlp2_max": (_int, [_vp] * 11 + [ctypes.c_int32, ctypes.c_int32, _i64, _i64, ctypes.c_int32, _vp, _vp]),
+    "spx_dense_select_ws_bytes": (_sz, [ctypes.c_int32, _i64, ctypes.c_int32, _i64]),
+    "spx_dense_select": (_int, [_vp, _vp, ctypes.c_int32, _i64, _f32p, ctypes.c_int32, _i64, _int, _vp, _vp, _vp, _sz,
+                                _vp]),
+    "spx_dense_post_process_ws_bytes": (_sz, [ctypes.c_int32, _i64, ctypes.c_int32, _i64, _i64]),
+    "spx_dense_post_process": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _f32p, ctypes.c_int32,
+                                      ctypes.c_float, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

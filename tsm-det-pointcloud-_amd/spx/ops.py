@@ -2444,3 +2444,100 @@ def sa_mlp2_max(P, xyz, new_xyz, idx, empty, Wx, a1, b1, W2, a2, b2):
                               _ptr(W2), _ptr(a2), _ptr(b2), c1, c2, n_src, m, s, _ptr(out), _stream(xyz)),
           "spx_sa_mlp2_max")
     return out
+
+
+# ------------------------------------------------------------------- dense-prediction post-processing (§29)
+
+DENSE_POST_PROCESS_MAX_PRE = 16384   # candidates per (frame, class) that go into an NMS: their keys sit in one CU's LDS
+
+
+def _dense_args(what, scores, labels, boxes, batch_size, thresholds, pre_max, post_max, per_class):
+    """The shape and limit checks the two dense ops share -> (b, n, thresholds or None, n_thresh).  Host values only."""
+    b = int(batch_size)
+    if thresholds is not None:
+        thresholds = [float(t) for t in (thresholds if isinstance(thresholds, (list, tuple)) else [thresholds])]
+    bad = scores.dim() != 1 or labels.shape != scores.shape or b < 0 or (b == 0 and scores.shape[0] != 0) \
+        or (b > 0 and scores.shape[0] % b != 0)
+    if boxes is not None:
+        bad = bad or boxes.dim() != 2 or boxes.shape[0] != scores.shape[0] or boxes.shape[1] < 7
+    if bad:
+        raise _lib.SpxError("%s: scores %s, labels %s%s do not make %d equal frames"
+                            % (what, tuple(scores.shape), tuple(labels.shape),
+                               "" if boxes is None else ", boxes %s" % (tuple(boxes.shape),), b))
+    nt = 1 if thresholds is None else len(thresholds)
+    if not per_class and nt != 1:
+        raise _lib.SpxError("%s: class-agnostic mode takes one threshold, got %d" % (what, nt))
+    if thresholds is None and per_class:
+        raise _lib.SpxError("%s: thresholds=None (no threshold) goes with per_class=False" % what)
+    if not 1 <= nt <= 8:
+        raise _lib.SpxError("%s: 1 .. 8 thresholds, got %d" % (what, nt))
+    if not 1 <= int(pre_max) <= DENSE_POST_PROCESS_MAX_PRE:
+        raise _lib.SpxError("%s: pre_max %d outside 1 .. %d" % (what, int(pre_max), DENSE_POST_PROCESS_MAX_PRE))
+    if post_max is not None and int(post_max) < 1:
+        raise _lib.SpxError("%s: post_max %d < 1" % (what, int(post_max)))
+    if scores.shape[0] >= 2 ** 31 or b > 65535:
+        raise _lib.SpxError("%s: %d rows in %d frames are too many" % (what, scores.shape[0], b))
+    n = scores.shape[0] // b if b > 0 else 0
+    if post_max is not None and nt * min(int(post_max), int(pre_max), max(n, 1)) > POST_PROCESS_MAX_N:
+        raise _lib.SpxError("%s: %d classes x %d kept boxes exceed the %d survivors the final stage takes"
+                            % (what, nt, min(int(post_max), int(pre_max), n), POST_PROCESS_MAX_N))
+    return b, n, thresholds, nt
+
+
+def dense_select(scores, labels, batch_size, thresholds, pre_max, per_class=True):
+    """spx_dense_select: scores (B * n) normalised, labels (B * n) 1-based, frames contiguous with n rows each (any n);
+    thresholds one float per class (per_class), a single one, or None for no threshold (per_class=False) ->
+    cand (B, T, pre_max) int64: per (frame, class) the members by score descending, equal scores lower row first, as rows
+    of the input, -1 past the count; count (B, T) int32.  A NaN score is never a member.  No host read."""
+    b, n, thresholds, nt = _dense_args("dense_select", scores, labels, None, batch_size, thresholds, pre_max, None,
+                                       per_class)
+    _need_gpu(scores, labels)
+    lib = _lib.load()
+    dev = scores.device
+    pre_max = int(pre_max)
+    if b * n == 0:
+        return (torch.full((b, nt, pre_max), -1, dtype=torch.int64, device=dev),
+                torch.zeros((b, nt), dtype=torch.int32, device=dev))
+    scores, labels = _f32(scores), _i32(labels)
+    cand = torch.empty((b, nt, pre_max), dtype=torch.int64, device=dev)
+    count = torch.empty((b, nt), dtype=torch.int32, device=dev)
+    wsb = lib.spx_dense_select_ws_bytes(b, n, nt, pre_max)
+    ws = workspace(dev, wsb)
+    check(lib.spx_dense_select(_ptr(scores), _ptr(labels), b, n, None if thresholds is None else f_arr(thresholds), nt,
+                               pre_max, int(bool(per_class)), _ptr(cand), _ptr(count), _ptr(ws), wsb, _stream(scores)),
+          "spx_dense_select")
+    return cand, count
+
+
+def dense_post_process(scores, labels, boxes, batch_size, thresholds, nms_thresh, pre_max, post_max, axis_aligned=False,
+                       per_class=True):
+    """spx_dense_post_process: point_post_process for any n -- scores (B * n) normalised, labels (B * n) 1-based, boxes
+    (B * n, >= 7) read by their row stride; thresholds one float per class (per_class, the fork's multi_thresh), a single
+    one (class-agnostic NMS) or None (no threshold, per_class=False: proposals) -> the dict of point_post_process: sel
+    (B, K) int64 rows of the input or -1, count (B) int32, boxes (B, K, 7), scores (B, K), labels (B, K) int64, zeros
+    past count.  pre_max <= DENSE_POST_PROCESS_MAX_PRE.  No host read."""
+    b, n, thresholds, nt = _dense_args("dense_post_process", scores, labels, boxes, batch_size, thresholds, pre_max,
+                                       post_max, per_class)
+    _need_gpu(scores, labels, boxes)
+    lib = _lib.load()
+    dev = scores.device
+    scores, labels, boxes = _f32(scores), _i32(labels), boxes.detach()
+    if boxes.dtype != torch.float32 or boxes.stride(1) != 1 or boxes.stride(0) < boxes.shape[1] or b * n == 0:
+        boxes = boxes.contiguous().float()
+    k = int(lib.spx_point_post_process_capacity(n, nt, int(post_max), int(bool(per_class))))
+    out = {"sel": torch.empty((b, k), dtype=torch.int64, device=dev),
+           "count": torch.empty((b,), dtype=torch.int32, device=dev),
+           "boxes": torch.empty((b, k, 7), dtype=torch.float32, device=dev),
+           "scores": torch.empty((b, k), dtype=torch.float32, device=dev),
+           "labels": torch.empty((b, k), dtype=torch.int64, device=dev)}
+    if b * k == 0:
+        out["count"].zero_()      # frames without candidates: nothing to launch (and no storage to point at)
+        return out
+    wsb = lib.spx_dense_post_process_ws_bytes(b, n, nt, int(pre_max), int(post_max))
+    ws = workspace(dev, wsb)
+    check(lib.spx_dense_post_process(_ptr(scores), _ptr(labels), _ptr(boxes), boxes.stride(0), b, n,
+                                     None if thresholds is None else f_arr(thresholds), nt, float(nms_thresh),
+                                     int(pre_max), int(post_max), int(bool(axis_aligned)), int(bool(per_class)),
+                                     _ptr(out["sel"]), _ptr(out["count"]), _ptr(out["boxes"]), _ptr(out["scores"]),
+                                     _ptr(out["labels"]), _ptr(ws), wsb, _stream(scores)), "spx_dense_post_process")
+    return out
