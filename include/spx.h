@@ -510,8 +510,8 @@ int spx_group_points(const float *features, const int32_t *idx, int32_t b, int32
                      int32_t nsample, float *out, spx_stream_t stream);
 
 /* replaces: group_points_grad_wrapper / gather_points_grad_wrapper (atomicAdd there).  grad_features [b, c, n] (fully
- *   written) = sum of grad_out over the entries that point at each feature, DETERMINISTIC: the entries are sorted by
- *   target (stable radix sort in ws) and each target's contributions are added in ascending entry order. */
+ *   written) = sum of grad_out over the entries that point at each feature, DETERMINISTIC: sorted runs by target
+ *   b * n + k, added in ascending entry order (the contract is stated once, in csrc/sorted_runs.h). */
 size_t spx_group_points_bwd_ws_bytes(int32_t b, int64_t n, int64_t m, int32_t nsample);
 int spx_group_points_bwd(const float *grad_out, const int32_t *idx, int32_t b, int32_t c, int64_t n, int64_t m,
                          int32_t nsample, float *grad_features, void *ws, size_t ws_bytes, spx_stream_t stream);
@@ -595,7 +595,7 @@ int spx_group_project(const float *p, const float *wx, const float *xyz, const f
 
 /* Backward of spx_group_project.  dy [b, c_out, npoint, nsample].  Either output may be NULL (not computed):
  *   dpt [c_out, n_src] (TRANSPOSED, fully written): dP^T[o, r] = sum of dy[.., o, ..] over the non-empty columns with
- *     idx = r, DETERMINISTIC: columns stable-sorted by r, each run added in ascending column order (dF = dP · Wf and
+ *     idx = r, DETERMINISTIC: sorted runs by r (csrc/sorted_runs.h), added in ascending column order (dF = dP · Wf and
  *     dWf = dP^T · F are the caller's GEMMs);
  *   dwx [c_out, 3]: sum over non-empty columns of dy * (xyz[r] - ctr[m]), DETERMINISTIC: fixed-order per-block partials
  *     over chunks of 2048 columns, then a fixed-order sum of the partials.
@@ -812,9 +812,9 @@ int spx_stack_group_points(const float *features, const int32_t *features_batch_
                            int32_t nsample, float *out, spx_stream_t stream);
 
 /* replaces: group_points_grad_wrapper (atomicAdd there).  grad_out [m_rows, c, nsample] -> grad_features [n_rows, c],
- *   every element written, DETERMINISTIC and without float atomics: the entries are stable-sorted by global target row
- *   (radix sort in ws), each target's run is added in ascending entry order in pieces of at most 128 sorted positions,
- *   and the pieces of a run that crosses such a border are added in ascending order afterwards. */
+ *   every element written, DETERMINISTIC and without float atomics: sorted runs by global target row
+ *   (csrc/sorted_runs.h), each run added in ascending entry order in pieces of at most 128 sorted positions, and the
+ *   pieces of a run that crosses such a border added in ascending order afterwards. */
 size_t spx_stack_group_points_bwd_ws_bytes(int64_t n_rows, int64_t m_rows, int32_t c, int32_t nsample);
 int spx_stack_group_points_bwd(const float *grad_out, const int32_t *features_batch_cnt, const int32_t *idx,
                                const int32_t *idx_batch_cnt, int32_t b, int64_t n_rows, int64_t m_rows, int32_t c,
@@ -1209,8 +1209,8 @@ int spx_voxel_pool_max_fwd(const float *f, const float *xyz, const float *new_xy
 /* Backward of spx_voxel_pool_max_fwd.  dout [m, c], arg from the forward; g = dout[m, ch] where arg >= 0, else 0.  Any
  *   output may be NULL (not computed), not all:
  *   df [n_src, c], fully written (0 where nothing points): df[r, ch] = sum of g over the (m, ch) whose winning slot
- *     points at r (non-empty queries only), DETERMINISTIC: the (m, s) entries are stable-sorted by r and each run is
- *     added in ascending m;
+ *     points at r (non-empty queries only), DETERMINISTIC: sorted runs of the (m, s) entries by r
+ *     (csrc/sorted_runs.h), each run added in ascending m;
  *   da [c, 3] = sum_m g * d(m, arg), db [c] = sum_m g, DETERMINISTIC: per-block partials over chunks of 128 queries
  *     (four interleaved ascending sub-sums, added in order), then a fixed-order sum of the partials.
  *   No gradient flows to xyz or new_xyz.  ws: spx_voxel_pool_max_bwd_ws_bytes bytes. */

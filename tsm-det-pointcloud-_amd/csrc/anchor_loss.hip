@@ -8,7 +8,7 @@
 // launches forward and ~150 backward on [B, 211200, *] tensors; here one thread per anchor computes its three loss terms
 // and d(loss)/d(prediction) at once, block sums go to a partial array and a last kernel adds them in fixed order (no
 // float atomics: bitwise reproducible).  Normalisers are the per-frame positive counts, as in the reference.
-#include "spx_common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -53,16 +53,6 @@ __global__ __launch_bounds__(1024) void k_count_pos(const int32_t* __restrict__ 
     for (int i = 0; i < 16; ++i) t += s[i];
     npos[b] = t;
   }
-}
-
-__device__ __forceinline__ float block_sum(float v, float* sm) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  if (threadIdx.x == 0) t = sm[0] + sm[1] + sm[2] + sm[3];
-  __syncthreads();
-  return t;
 }
 
 __global__ __launch_bounds__(256) void k_anchor_loss(LossArgs g, const int32_t* __restrict__ npos, float* __restrict__ partial,
@@ -155,7 +145,7 @@ __global__ __launch_bounds__(256) void k_anchor_loss(LossArgs g, const int32_t* 
     }
   }
   const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-  float s0 = block_sum(l_cls, sm), s1 = block_sum(l_loc, sm), s2 = block_sum(l_dir, sm);
+  float s0 = spx_block_sum(l_cls, sm), s1 = spx_block_sum(l_loc, sm), s2 = spx_block_sum(l_dir, sm);
   if (threadIdx.x == 0) {
     partial[blk * 3 + 0] = s0;
     partial[blk * 3 + 1] = s1;
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(256) void k_loss_final(const float* __restrict__ pa
     for (int c = 0; c < 3; ++c) s[c] += partial[i * 3 + c];
   const float scale[3] = {g.cls_w / (float)g.B, g.loc_w / (float)g.B, g.dir_w / (float)g.B};
   for (int c = 0; c < 3; ++c) {
-    float t = block_sum(s[c], sm);
+    float t = spx_block_sum(s[c], sm);
     if (threadIdx.x == 0) out[c] = t * scale[c];
   }
 }

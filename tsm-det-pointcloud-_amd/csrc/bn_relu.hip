@@ -112,6 +112,7 @@ __global__ __launch_bounds__(256) void k_bn_reduce(const float* __restrict__ x, 
 }
 
 // one wave per channel: lane l adds partials l, l+64, ... in fp64, then a fixed-order shuffle tree
+// (a pair per step, shuffle-down: not block_ops.h's spx_wave_sum, and block_sum2 below adds its rows in its own order)
 __device__ __forceinline__ void wave_sum2(double& s, double& q) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {

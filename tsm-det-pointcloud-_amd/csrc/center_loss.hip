@@ -25,7 +25,7 @@
 // Precision: sigmoid(x) and sigmoid(-x) are each computed from exp(-|x|), and a log is taken of the smaller of the two
 // directly and of the larger as log1p(-smaller), so neither tail loses digits to 1 - p; sums are double.  heatmap values are taken to lie in [0, 1]: a cell equal to 1 is a
 // positive, every other cell a negative with weight (1 - gt)^4.
-#include "spx_common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -49,16 +49,6 @@ struct RegMaps {
   float cw[kMaxD];                // code weights
 };
 
-template <typename T>
-__device__ __forceinline__ T block_sum_all(T v, T* sm) {   // the block's sum in every thread; sm[4]
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const T t = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-  __syncthreads();
-  return t;
-}
-
 // ---------------------------------------------------------------------------------------------------------- launch 1
 __global__ __launch_bounds__(kBlock) void k_count_zero(const float* __restrict__ heatmap, int64_t n, int hvec, RegMaps m,
                                                        int64_t bhw, int32_t* __restrict__ pos_part) {
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void k_count_zero(const float* __restrict__
     for (int64_t i = tid; i < nr4; i += stride) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int64_t i = nr4 * 4 + tid; i < nr; i += stride) g[i] = 0.f;
   }
-  c = block_sum_all(c, sm);
+  c = spx_block_sum_all(c, sm);
   if (threadIdx.x == 0) pos_part[blockIdx.x] = c;
 }
 
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_focal_reg(LossArgs a, RegMaps m) {
   __shared__ int s_last;
   const int t = threadIdx.x;
   if ((int)blockIdx.x < a.n_focal) {
-    const int np = block_sum_all(t < a.n_count ? a.pos_part[t] : 0, sm_i);
+    const int np = spx_block_sum_all(t < a.n_count ? a.pos_part[t] : 0, sm_i);
     const float gscale = a.cls_weight / fmaxf((float)np, 1.f);
     const int64_t base = (int64_t)blockIdx.x * kPerBlock;
     double s = 0.0;
@@ -161,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_focal_reg(LossArgs a, RegMaps m) {
         }
       }
     }
-    s = block_sum_all(s, sm_d);
+    s = spx_block_sum_all(s, sm_d);
     if (t == 0) a.foc_part[blockIdx.x] = s;
     return;
   }
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_focal_reg(LossArgs a, RegMaps m) {
   const int rb = (int)blockIdx.x - a.n_focal, f = rb / a.split, part = rb % a.split;
   int c = 0;
   for (int64_t i = t; i < (int64_t)a.b * a.k; i += kBlock) c += a.masks[i] == 1;
-  const int num = block_sum_all(c, sm_i);
+  const int num = spx_block_sum_all(c, sm_i);
   if (rb == 0 && t == 0) a.num[0] = num;
   if (t == 0) s_last = -1;
   __syncthreads();
@@ -219,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void k_focal_reg(LossArgs a, RegMaps m) {
   }
 #pragma unroll
   for (int col = 0; col < kMaxD; ++col) {
-    const double s = block_sum_all(l[col], sm_d);
+    const double s = spx_block_sum_all(l[col], sm_d);
     if (t == 0) a.reg_part[(int64_t)rb * kMaxD + col] = s;
   }
 }
@@ -231,10 +221,10 @@ __global__ __launch_bounds__(kBlock) void k_final(LossArgs a, RegMaps m, float* 
   __shared__ double sm_d[4];
   __shared__ double s_col[kMaxD];
   const int t = threadIdx.x;
-  const int np = block_sum_all(t < a.n_count ? a.pos_part[t] : 0, sm_i);
+  const int np = spx_block_sum_all(t < a.n_count ? a.pos_part[t] : 0, sm_i);
   double s = 0.0;
   for (int i = t; i < a.n_focal; i += kBlock) s += a.foc_part[i];
-  s = block_sum_all(s, sm_d);
+  s = spx_block_sum_all(s, sm_d);
   if (t == 0) losses[0] = (float)(-s / (double)(np > 1 ? np : 1) * (double)a.cls_weight);
   if (t < m.d) {
     double r = 0.0;

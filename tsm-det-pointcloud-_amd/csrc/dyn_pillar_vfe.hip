@@ -37,7 +37,7 @@
 // Integer atomics only (bitmap OR, count, the large-pillar list; nothing that is kept depends on their order), no float
 // atomics, no host read, every floating sum in double in a fixed order.  Rows at or beyond min(*d_num_pillars, cap) and
 // positions at or beyond *d_num_points are never dereferenced.
-#include "spx_common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -59,24 +59,6 @@ constexpr int kScanRows = 4 * kBlock;         // rows of `count` per block of th
 constexpr int kBwdRows = 16;                  // pillars per tile of k_bwd_gather
 
 // ------------------------------------------------------------------------------------------------ block helpers
-// exclusive scan over the 256 threads of a block; wsum: 4 words of LDS
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total, uint32_t* wsum) {
-  const int lane = spx_lane(), wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  if (total) *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return base + inc - v;
-}
-
 // sum of a[0 .. b) by the whole block (integers: the order does not matter)
 __device__ __forceinline__ uint32_t block_sum_before(const uint32_t* __restrict__ a, int64_t b, uint32_t* wsum) {
   uint32_t s = 0;
@@ -140,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_blocksum(const uint64_t* __restrict_
   const int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t s = w < nwords ? (uint32_t)__popcll(bits[w]) : 0u;
   uint32_t total;
-  block_excl_scan(s, &total, wsum);
+  spx_block_excl_scan(s, &total, wsum);
   if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
   for (int64_t r = w; r < cap; r += (int64_t)gridDim.x * kBlock) count[r] = 0;
   if (w == 0) *n_big = 0;
@@ -155,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(const uint64_t* __restrict__ 
   const int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   uint64_t m = w < nwords ? bits[w] : 0ull;
   uint32_t total;
-  uint32_t run = base + block_excl_scan((uint32_t)__popcll(m), &total, wsum);
+  uint32_t run = base + spx_block_excl_scan((uint32_t)__popcll(m), &total, wsum);
   if (w < nwords) prefix[w] = run;
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
     const int64_t np = (int64_t)base + total;
@@ -204,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void k_count_blocksum(const int32_t* __rest
   for (int j = 0; j < 4; ++j)
     if (r0 + j < cap) s += (uint32_t)count[r0 + j];
   uint32_t total;
-  block_excl_scan(s, &total, wsum);
+  spx_block_excl_scan(s, &total, wsum);
   if (threadIdx.x == 0) cblock[blockIdx.x] = total;
 }
 
@@ -220,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_offsets(const int32_t* __restrict__ 
     c[j] = r0 + j < cap ? (uint32_t)count[r0 + j] : 0u;
     s += c[j];
   }
-  uint32_t run = base + block_excl_scan(s, nullptr, wsum);
+  uint32_t run = base + spx_block_excl_scan(s, nullptr, wsum);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (r0 + j <= cap) offset[r0 + j] = (int32_t)run;
@@ -295,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void k_order_big(const int32_t* __restrict_
         for (int u = 0; u < 8; ++u)
           if (b + u < n && inv[b + u] == (int32_t)p) mask |= 1u << u;
         uint32_t total;
-        uint32_t dst = base + block_excl_scan((uint32_t)__popc(mask), &total, wsum);
+        uint32_t dst = base + spx_block_excl_scan((uint32_t)__popc(mask), &total, wsum);
 #pragma unroll
         for (int u = 0; u < 8; ++u)
           if ((mask >> u) & 1u) {

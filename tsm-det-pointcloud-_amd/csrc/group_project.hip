@@ -9,15 +9,14 @@
 //
 // The xyz term stays relative: folding Wx·xyz into P would subtract two ~70 m products to get a ~1 m one.
 // Backward, deterministic (no float atomics):
-//   dP^T[o, r] = sum of dY[m, s, o] over the live (m, s) with idx = r: entries are stable-radix-sorted by r, then every
-//                (o, r) adds its run in ascending entry order (the scheme of spx_group_points_bwd);
+//   dP^T[o, r] = sum of dY[m, s, o] over the live (m, s) with idx = r: sorted runs by r (sorted_runs.h), then every
+//                (o, r) adds its run in ascending entry order;
 //   dWx[o, j]  = sum over live columns of dY * rel: each block sums a fixed chunk of columns (wave shuffles, then the
 //                four waves in order), one block per output then adds the per-block partials in a fixed order.
 // dWx is a K = 3 GEMM over ~2 M columns: memory bound on reading dY, and a 16x16x4 f32 MFMA would use 3 of its 16 N
 // columns, so it stays on the VALU.
-#include "spx_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "block_ops.h"
+#include "sorted_runs.h"
 
 namespace {
 
@@ -101,17 +100,6 @@ __global__ __launch_bounds__(kThreads) void k_gp_keys(const int32_t* __restrict_
   vals[col] = (uint32_t)col;
 }
 
-__global__ __launch_bounds__(kThreads) void k_gp_bounds(const uint32_t* __restrict__ keys, int64_t total,
-                                                        uint32_t sentinel, int32_t* __restrict__ start,
-                                                        int32_t* __restrict__ end) {
-  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (q >= total) return;
-  const uint32_t k = keys[q];
-  if (k == sentinel) return;
-  if (q == 0 || keys[q - 1] != k) start[k] = (int32_t)q;
-  if (q == total - 1 || keys[q + 1] != k) end[k] = (int32_t)(q + 1);
-}
-
 // dpt[o][r] = sum over r's sorted run of dY at (o, column), in ascending column order
 __global__ __launch_bounds__(kThreads) void k_gp_dp(const float* __restrict__ dy, const uint32_t* __restrict__ vals,
                                                     const int32_t* __restrict__ start, const int32_t* __restrict__ end,
@@ -127,12 +115,6 @@ __global__ __launch_bounds__(kThreads) void k_gp_dp(const float* __restrict__ dy
 }
 
 // ---------------------------------------------------------------------------------------------- dWx
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, SPX_WAVE);
-  return v;
-}
-
 // part[blk][o][j] = sum over the block's columns of dY[o, col] * rel[col, j]
 __global__ __launch_bounds__(kThreads) void k_gp_dwx_part(const float* __restrict__ dy, const float* __restrict__ xyz,
                                                           const float* __restrict__ ctr, const int32_t* __restrict__ idx,
@@ -173,9 +155,9 @@ __global__ __launch_bounds__(kThreads) void k_gp_dwx_part(const float* __restric
         a1 += d * rel[i][1];
         a2 += d * rel[i][2];
       }
-      a0 = wave_sum(a0);
-      a1 = wave_sum(a1);
-      a2 = wave_sum(a2);
+      a0 = spx_wave_sum(a0);
+      a1 = spx_wave_sum(a1);
+      a2 = spx_wave_sum(a2);
       if (lane == 0) {
         s_w[wave][t * 3 + 0] = a0;
         s_w[wave][t * 3 + 1] = a1;
@@ -193,57 +175,17 @@ __global__ __launch_bounds__(kThreads) void k_gp_dwx_part(const float* __restric
   }
 }
 
-// dwx[q] = sum over blocks of part[blk][q]: one block per q, thread t adds blocks t, t + 256, ... then a fixed tree
-__global__ __launch_bounds__(kThreads) void k_gp_dwx_final(const float* __restrict__ part, int64_t nblk, int nq,
-                                                           float* __restrict__ dwx) {
-  __shared__ float s_v[kThreads];
-  const int q = blockIdx.x, tid = threadIdx.x;
-  float v = 0.f;
-  for (int64_t k = tid; k < nblk; k += kThreads) v += part[(size_t)k * nq + q];
-  s_v[tid] = v;
-  __syncthreads();
-  for (int h = kThreads / 2; h > 0; h >>= 1) {
-    if (tid < h) s_v[tid] += s_v[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) dwx[q] = s_v[0];
-}
-
-unsigned key_bits(uint64_t sentinel) {
-  unsigned bits = 1;
-  while (bits < 32 && (sentinel >> bits) != 0) ++bits;
-  return bits;
-}
-
-struct BwdWs {
-  uint32_t *keys_in, *vals_in, *keys_out, *vals_out;
-  int32_t *start, *end;
-  void* sort_tmp;
-  float* part;
-  size_t sort_bytes;
+struct BwdWs : SortedRunsWs {
+  float* part;   // dWx: [dwx_blocks][c_out][3]
 };
 
 int64_t dwx_blocks(int64_t total) { return (total + kColsPerBlock - 1) / kColsPerBlock; }
 
+// the sorted-runs block, then part
 size_t bwd_ws_layout(int64_t total, int64_t n_src, int c_out, char* base, BwdWs* ws) {
-  size_t sort_bytes = 0;
-  (void)rocprim::radix_sort_pairs((void*)nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)total, 0,
-                                  key_bits((uint64_t)n_src));
-  const size_t a = spx_align((size_t)total * 4), t = spx_align((size_t)n_src * 4), sb = spx_align(sort_bytes);
-  const size_t pb = spx_align((size_t)dwx_blocks(total) * c_out * 3 * 4);
-  if (ws) {
-    ws->keys_in = (uint32_t*)base;
-    ws->vals_in = (uint32_t*)(base + a);
-    ws->keys_out = (uint32_t*)(base + 2 * a);
-    ws->vals_out = (uint32_t*)(base + 3 * a);
-    ws->start = (int32_t*)(base + 4 * a);
-    ws->end = (int32_t*)(base + 4 * a + t);
-    ws->sort_tmp = base + 4 * a + 2 * t;
-    ws->part = (float*)(base + 4 * a + 2 * t + sb);
-    ws->sort_bytes = sb;
-  }
-  return 4 * a + 2 * t + sb + pb;
+  const size_t sr = spx_sorted_runs_layout(total, n_src, base, ws);
+  if (ws) ws->part = (float*)(base + sr);
+  return sr + spx_align((size_t)dwx_blocks(total) * c_out * 3 * 4);
 }
 
 int check_geom(int32_t c_out, int64_t n_src, int32_t b, int64_t npoint, int32_t nsample, Geom* g) {
@@ -311,20 +253,10 @@ extern "C" int spx_group_project_bwd(const float* dy, const float* xyz, const fl
   bwd_ws_layout(g.total, n_src, c_out, (char*)ws, &L);
   hipStream_t s = spx_s(stream);
   if (dpt && n_src > 0) {
-    const uint32_t sentinel = (uint32_t)n_src;
-    if (g.total > 0) {
+    if (g.total > 0)
       hipLaunchKernelGGL(k_gp_keys, dim3((unsigned)((g.total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, idx,
                          empty, g, L.keys_in, L.vals_in);
-      size_t sb = L.sort_bytes;
-      if (rocprim::radix_sort_pairs(L.sort_tmp, sb, L.keys_in, L.keys_out, L.vals_in, L.vals_out, (size_t)g.total, 0,
-                                    key_bits(sentinel), s) != hipSuccess)
-        return SPX_ERR_LAUNCH;
-    }
-    // start and end are adjacent in ws (with the alignment gap): one fill zeroes both
-    spx_fill_async(L.start, 0, (size_t)((char*)(L.end + n_src) - (char*)L.start), s);
-    if (g.total > 0)
-      hipLaunchKernelGGL(k_gp_bounds, dim3((unsigned)((g.total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                         L.keys_out, g.total, sentinel, L.start, L.end);
+    if (const int e = spx_sorted_runs(L, g.total, n_src, s); e != SPX_OK) return e;
     hipLaunchKernelGGL(k_gp_dp, dim3((unsigned)((n_src + kThreads - 1) / kThreads), (unsigned)c_out), dim3(kThreads), 0,
                        s, dy, L.vals_out, L.start, L.end, g, dpt);
   }
@@ -332,7 +264,7 @@ extern "C" int spx_group_project_bwd(const float* dy, const float* xyz, const fl
     const int64_t nblk = dwx_blocks(g.total);
     if (nblk > 0)
       hipLaunchKernelGGL(k_gp_dwx_part, dim3((unsigned)nblk), dim3(kThreads), 0, s, dy, xyz, ctr, idx, empty, g, L.part);
-    hipLaunchKernelGGL(k_gp_dwx_final, dim3((unsigned)(c_out * 3)), dim3(kThreads), 0, s, L.part, nblk, c_out * 3, dwx);
+    hipLaunchKernelGGL(spx_k_column_sum<float>, dim3((unsigned)(c_out * 3)), dim3(256), 0, s, L.part, nblk, c_out * 3, dwx);
   }
   SPX_CHECK_LAUNCH();
   return SPX_OK;

@@ -13,7 +13,7 @@
 //
 // Ties: where the reference takes min / max / clamp of two equal operands (measure zero in real data) torch splits the
 // gradient between them; here the FIRST operand takes it, and clamp passes the gradient at its bound as torch does.
-#include "spx_common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -62,16 +62,6 @@ __global__ __launch_bounds__(1024) void k_head_counts(const int64_t* __restrict_
     for (int i = 0; i < 16; ++i) t += s[threadIdx.x][i];
     counts[threadIdx.x] = t;
   }
-}
-
-__device__ __forceinline__ float block_sum(float v, float* sm) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  if (threadIdx.x == 0) t = sm[0] + sm[1] + sm[2] + sm[3];
-  __syncthreads();
-  return t;
 }
 
 // smooth L1 of diff and its derivative (WeightedSmoothL1Loss.smooth_l1_loss; beta < 1e-5: L1)
@@ -336,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_head_rows(HeadArgs g, const int32_t*
     head_row(g, r, inv_nv, inv_nc, inv_np, d_vote, d_cls, d_reg, d_box, l);
   }
   for (int c = 0; c < 3; ++c) {
-    const float s = block_sum(l[c], sm);
+    const float s = spx_block_sum(l[c], sm);
     if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * 3 + c] = s;
   }
 }
@@ -348,7 +338,7 @@ __global__ __launch_bounds__(kBlock) void k_sum_partials(const float* __restrict
   for (int c = 0; c < ncomp; ++c) {
     float s = 0.f;
     for (int64_t i = threadIdx.x; i < nblk; i += kBlock) s += partial[i * ncomp + c];
-    const float t = block_sum(s, sm);
+    const float t = spx_block_sum(s, sm);
     if (threadIdx.x == 0) out[c] = t;
   }
 }
@@ -410,7 +400,7 @@ __global__ __launch_bounds__(kBlock) void k_seg_rows(const float* __restrict__ s
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   float l = 0.f;
   if (r < n) l = seg_row(scores, labels, r, S, num_class, func, layer_weight / fmaxf((float)count[0], 1.f), d_scores);
-  const float s = block_sum(l, sm);
+  const float s = spx_block_sum(l, sm);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 

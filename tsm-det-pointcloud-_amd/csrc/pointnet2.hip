@@ -15,9 +15,7 @@
 //     k with the smallest (bitrev_log2(bs)(k mod bs), k div bs).  That priority is the low half of a 64-bit key whose
 //     high half is the value as an order-preserving uint, so any reduction order gives the reference's pick.  A thread
 //     whose values are all <= -1 reports nothing (the reference's `best = -1` start); no candidate at all picks 0.
-#include "spx_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "sorted_runs.h"
 
 #pragma clang fp contract(off)
 
@@ -255,8 +253,8 @@ __global__ __launch_bounds__(256) void k_group(const float* __restrict__ f, cons
   out[((size_t)b * C + c) * E + e] = (k >= 0 && k < N) ? f[((size_t)b * C + c) * N + k] : 0.f;
 }
 
-// Deterministic scatter-add backward: entries are sorted by target (b*N + k, stable, so each target's contributions
-// stay in ascending entry order), then one thread per (b, c, k) sums its run in that order — no float atomics.
+// Deterministic scatter-add backward on sorted runs (sorted_runs.h): the key of an entry is its target b*N + k, then one
+// thread per (b, c, k) sums its run in ascending entry order — no float atomics.
 __global__ __launch_bounds__(256) void k_scatter_keys(const int32_t* __restrict__ idx, int64_t total, int64_t per_frame,
                                                       int N, uint32_t sentinel, uint32_t* __restrict__ keys,
                                                       uint32_t* __restrict__ vals) {
@@ -265,21 +263,6 @@ __global__ __launch_bounds__(256) void k_scatter_keys(const int32_t* __restrict_
   const int32_t k = idx[e];
   keys[e] = (k >= 0 && k < N) ? (uint32_t)((e / per_frame) * N + k) : sentinel;
   vals[e] = (uint32_t)e;
-}
-
-__global__ __launch_bounds__(256) void k_run_bounds(const uint32_t* __restrict__ keys, int64_t total, uint32_t sentinel,
-                                                    int32_t* __restrict__ start, int32_t* __restrict__ end) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= total) return;
-  const uint32_t k = keys[p];
-  if (k == sentinel) return;
-  if (p == 0 || keys[p - 1] != k) start[k] = (int32_t)p;
-  if (p == total - 1 || keys[p + 1] != k) end[k] = (int32_t)(p + 1);
-}
-
-__global__ __launch_bounds__(256) void k_zero_i32(int32_t* __restrict__ p, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0;
 }
 
 // grad_f[b][c][k] = sum over the sorted run of target b*N + k of g[b][c][e / G] * (w ? w[e] : 1), e the entry
@@ -304,64 +287,18 @@ __global__ __launch_bounds__(256) void k_scatter_sum(const float* __restrict__ g
   grad[((size_t)b * C + c) * N + k] = acc;
 }
 
-struct ScatterWs {
-  uint32_t *keys_in, *vals_in, *keys_out, *vals_out;
-  int32_t *start, *end;
-  void* sort_tmp;
-  size_t sort_bytes, total;
-};
-
-unsigned key_bits(uint64_t sentinel) {
-  unsigned bits = 1;
-  while (bits < 32 && (sentinel >> bits) != 0) ++bits;
-  return bits;
-}
-
-size_t sort_tmp_bytes(int64_t total, int64_t targets) {
-  size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs((void*)nullptr, bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (uint32_t*)nullptr, (size_t)total, 0, key_bits((uint64_t)targets));
-  return bytes;
-}
-
-size_t scatter_ws_layout(int64_t total, int64_t targets, char* base, ScatterWs* ws) {
-  const size_t a = spx_align((size_t)total * 4), t = spx_align((size_t)targets * 4);
-  const size_t sb = spx_align(sort_tmp_bytes(total, targets));
-  if (ws) {
-    ws->keys_in = (uint32_t*)base;
-    ws->vals_in = (uint32_t*)(base + a);
-    ws->keys_out = (uint32_t*)(base + 2 * a);
-    ws->vals_out = (uint32_t*)(base + 3 * a);
-    ws->start = (int32_t*)(base + 4 * a);
-    ws->end = (int32_t*)(base + 4 * a + t);
-    ws->sort_tmp = base + 4 * a + 2 * t;
-    ws->sort_bytes = sb;
-  }
-  return 4 * a + 2 * t + sb;
-}
-
 // idx [B, per_frame] int32 (targets in [0, N)), g [B, C, per_frame / G], w [B, per_frame] or NULL -> grad [B, C, N]
 int scatter_bwd(const float* g, const int32_t* idx, const float* w, int b, int c, int n, int64_t per_frame, int G,
                 float* grad, void* ws, size_t ws_bytes, hipStream_t s) {
   const int64_t total = (int64_t)b * per_frame, targets = (int64_t)b * n;
   if (total >= (int64_t)INT32_MAX || targets >= (int64_t)UINT32_MAX) return SPX_ERR_TOO_LARGE;
-  if (!ws || ws_bytes < scatter_ws_layout(total, targets, nullptr, nullptr)) return SPX_ERR_WORKSPACE;
-  ScatterWs L;
-  scatter_ws_layout(total, targets, (char*)ws, &L);
-  const uint32_t sentinel = (uint32_t)targets;
-  if (total > 0) {
-    hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx, total, per_frame, n,
-                       sentinel, L.keys_in, L.vals_in);
-    size_t sb = L.sort_bytes;
-    if (rocprim::radix_sort_pairs(L.sort_tmp, sb, L.keys_in, L.keys_out, L.vals_in, L.vals_out, (size_t)total, 0,
-                                  key_bits(sentinel), s) != hipSuccess)
-      return SPX_ERR_LAUNCH;
-  }
-  const int64_t bounds = (int64_t)(L.end - L.start) + targets;   // start, alignment gap, end
-  hipLaunchKernelGGL(k_zero_i32, dim3((unsigned)((bounds + 255) / 256)), dim3(256), 0, s, L.start, bounds);
+  if (!ws || ws_bytes < spx_sorted_runs_layout(total, targets, nullptr, nullptr)) return SPX_ERR_WORKSPACE;
+  SortedRunsWs L;
+  spx_sorted_runs_layout(total, targets, (char*)ws, &L);
   if (total > 0)
-    hipLaunchKernelGGL(k_run_bounds, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, L.keys_out, total, sentinel,
-                       L.start, L.end);
+    hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx, total, per_frame, n,
+                       (uint32_t)targets, L.keys_in, L.vals_in);
+  if (const int e = spx_sorted_runs(L, total, targets, s); e != SPX_OK) return e;
   hipLaunchKernelGGL(k_scatter_sum, dim3((unsigned)((n + 255) / 256), (unsigned)c, (unsigned)b), dim3(256), 0, s, g, w,
                      L.vals_out, L.start, L.end, c, n, per_frame, G, grad);
   SPX_CHECK_LAUNCH();
@@ -510,7 +447,7 @@ extern "C" int spx_group_points(const float* features, const int32_t* idx, int32
 
 extern "C" size_t spx_group_points_bwd_ws_bytes(int32_t b, int64_t n, int64_t m, int32_t nsample) {
   if (b <= 0 || n <= 0 || m < 0 || nsample <= 0) return 0;
-  return scatter_ws_layout((int64_t)b * m * nsample, (int64_t)b * n, nullptr, nullptr);
+  return spx_sorted_runs_layout((int64_t)b * m * nsample, (int64_t)b * n, nullptr, nullptr);
 }
 
 extern "C" int spx_group_points_bwd(const float* grad_out, const int32_t* idx, int32_t b, int32_t c, int64_t n, int64_t m,
@@ -549,7 +486,7 @@ extern "C" int spx_three_interpolate(const float* features, const int32_t* idx, 
 
 extern "C" size_t spx_three_interpolate_bwd_ws_bytes(int32_t b, int64_t m, int64_t n) {
   if (b <= 0 || m <= 0 || n < 0) return 0;
-  return scatter_ws_layout((int64_t)b * n * 3, (int64_t)b * m, nullptr, nullptr);
+  return spx_sorted_runs_layout((int64_t)b * n * 3, (int64_t)b * m, nullptr, nullptr);
 }
 
 extern "C" int spx_three_interpolate_bwd(const float* grad_out, const int32_t* idx, const float* weight, int32_t b,

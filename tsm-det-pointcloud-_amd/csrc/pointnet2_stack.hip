@@ -17,9 +17,7 @@
 //     counts; the grid is sized to the host-known bound ceil(m_rows / 256) + b and surplus workgroups skip the scan.
 //   - stack FPS ties: the reference always launches 1024 threads, whatever the frame's size, so the winner among equal
 //     maxima is the k with the smallest (bitrev10(k mod 1024), k div 1024): the 64-bit key of pointnet2.hip with L = 10.
-#include "spx_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "sorted_runs.h"
 
 #pragma clang fp contract(off)
 
@@ -256,9 +254,8 @@ __global__ __launch_bounds__(256) void k_stack_interp(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------- deterministic backward
-// Entries are given a key = global target row (or the sentinel = n_targets when they are dropped) and stable-sorted by
-// it, so each target's contributions form a run in ascending entry order.  The sorted array is cut into chunks of
-// kRunChunk positions; one thread per (chunk, channel) adds each run's piece inside its chunk in order.  A run that lies
+// Sorted runs (sorted_runs.h) with key = global target row.  The sorted array is cut into chunks of kRunChunk
+// positions; one thread per (chunk, channel) adds each run's piece inside its chunk in order.  A run that lies
 // inside one chunk is finished there.  A run that crosses chunk borders leaves one partial per chunk (at most one run
 // enters a chunk from the left and one leaves it to the right), and a second pass adds a target's partials in chunk
 // order: a heavy target costs ceil(len / kRunChunk) additions there instead of len, and the order stays fixed.
@@ -295,16 +292,6 @@ __global__ __launch_bounds__(256) void k_interp_keys(const int32_t* __restrict__
   const int32_t k = idx[e];
   keys[e] = (e / 3 < live && k >= 0 && k < m_rows) ? (uint32_t)k : (uint32_t)m_rows;
   vals[e] = (uint32_t)e;
-}
-
-__global__ __launch_bounds__(256) void k_run_bounds(const uint32_t* __restrict__ keys, int64_t total, uint32_t sentinel,
-                                                    int32_t* __restrict__ start, int32_t* __restrict__ end) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= total) return;
-  const uint32_t k = keys[p];
-  if (k == sentinel) return;
-  if (p == 0 || keys[p - 1] != k) start[k] = (int32_t)p;
-  if (p == total - 1 || keys[p + 1] != k) end[k] = (int32_t)(p + 1);
 }
 
 // WEIGHTED: entry = row * 3 + neighbour, contribution g[row][c] * w[entry]; else entry = row * nsample + slot,
@@ -360,46 +347,21 @@ __global__ __launch_bounds__(256) void k_run_finish(const int32_t* __restrict__ 
   grad[t] = acc;
 }
 
-struct ScatterWs {
-  uint32_t *keys_in, *vals_in, *keys_out, *vals_out;
-  int32_t *start, *end;
-  float *part_l, *part_r;
-  void* sort_tmp;
-  size_t sort_bytes;
+struct ScatterWs : SortedRunsWs {
+  float *part_l, *part_r;   // one partial per (chunk, channel) for the run that enters / leaves the chunk
 };
-
-unsigned key_bits(uint64_t sentinel) {
-  unsigned bits = 1;
-  while (bits < 32 && (sentinel >> bits) != 0) ++bits;
-  return bits;
-}
-
-size_t sort_tmp_bytes(int64_t total, int64_t targets) {
-  size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs((void*)nullptr, bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (uint32_t*)nullptr, (size_t)total, 0, key_bits((uint64_t)targets));
-  return bytes;
-}
 
 int64_t run_chunks(int64_t total) { return (total + kRunChunk - 1) / kRunChunk; }
 
+// the sorted-runs block (no sort temp when total == 0), then part_l | part_r
 size_t scatter_ws_layout(int64_t total, int64_t targets, int c, char* base, ScatterWs* ws) {
-  const size_t a = spx_align((size_t)total * 4), t = spx_align((size_t)targets * 4);
+  const size_t sr = spx_sorted_runs_layout(total, targets, base, ws, false);
   const size_t pp = spx_align((size_t)run_chunks(total) * (size_t)c * 4);
-  const size_t sb = spx_align(total > 0 ? sort_tmp_bytes(total, targets) : 0);
   if (ws) {
-    ws->keys_in = (uint32_t*)base;
-    ws->vals_in = (uint32_t*)(base + a);
-    ws->keys_out = (uint32_t*)(base + 2 * a);
-    ws->vals_out = (uint32_t*)(base + 3 * a);
-    ws->start = (int32_t*)(base + 4 * a);
-    ws->end = (int32_t*)(base + 4 * a + t);
-    ws->part_l = (float*)(base + 4 * a + 2 * t);
-    ws->part_r = (float*)(base + 4 * a + 2 * t + pp);
-    ws->sort_tmp = base + 4 * a + 2 * t + 2 * pp;
-    ws->sort_bytes = sb;
+    ws->part_l = (float*)(base + sr);
+    ws->part_r = (float*)(base + sr + pp);
   }
-  return 4 * a + 2 * t + 2 * pp + sb;
+  return sr + 2 * pp;
 }
 
 unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -408,15 +370,8 @@ unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 int scatter_sorted(const float* g, const float* w, const ScatterWs& L, int64_t total, int64_t targets, int c, int nsample,
                    float* grad, hipStream_t s) {
   const uint32_t sentinel = (uint32_t)targets;
+  if (const int e = spx_sorted_runs(L, total, targets, s); e != SPX_OK) return e;
   if (total > 0) {
-    size_t sb = L.sort_bytes;
-    if (rocprim::radix_sort_pairs(L.sort_tmp, sb, L.keys_in, L.keys_out, L.vals_in, L.vals_out, (size_t)total, 0,
-                                  key_bits(sentinel), s) != hipSuccess)
-      return SPX_ERR_LAUNCH;
-  }
-  spx_fill_async(L.start, 0, (size_t)((char*)L.part_l - (char*)L.start), s);   // start, end and the gap between
-  if (total > 0) {
-    hipLaunchKernelGGL(k_run_bounds, dim3(blocks_of(total)), dim3(256), 0, s, L.keys_out, total, sentinel, L.start, L.end);
     const int64_t threads = run_chunks(total) * c;
     if (w)
       hipLaunchKernelGGL((k_chunk_sums<true>), dim3(blocks_of(threads)), dim3(256), 0, s, g, w, L.keys_out, L.vals_out, total,

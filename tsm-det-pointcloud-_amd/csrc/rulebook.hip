@@ -11,7 +11,7 @@
 //
 // Replaces the indice-pair builders inside spconv.pytorch.{SubMConv3d,SparseConv3d}.forward, reference
 // call sites pcdet/models/backbones_3d/spconv_backbone.py:86-122 (spconv itself is not vendored).
-#include "spx_common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -246,25 +246,6 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ idx
 constexpr int kWordsPerThread = 1;   // one 64-cell word per thread: coalesced 8-byte loads, and the small dense grids of the deep levels (2-12 blocks at 8 words per thread, each thread decoding up to 8 x 64 cells serially: 30-48 us) spread over the chip
 constexpr int kWordsPerBlock = kBlock * kWordsPerThread;
 
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* total) {
-  // 256 threads = 4 waves.  wave-level inclusive scan by shuffles, then combine through LDS.
-  __shared__ uint32_t wsum[4];
-  int lane = spx_lane(), wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  if (total) *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return base + inc - v;
-}
-
 // exclusive scan of blocksum[0..nblk) in place by ONE block, total -> *d_n_out (+ capacity check)
 __device__ __forceinline__ void scan_top_body(uint32_t* blocksum, int64_t nblk, int64_t* d_n_out, int64_t cap,
                                               int32_t* status) {
@@ -275,7 +256,7 @@ __device__ __forceinline__ void scan_top_body(uint32_t* blocksum, int64_t nblk, 
     int64_t j = base + threadIdx.x;
     uint32_t v = j < nblk ? blocksum[j] : 0;
     uint32_t total;
-    uint32_t ex = block_exclusive_scan(v, &total);
+    uint32_t ex = spx_block_excl_scan(v, &total);
     uint32_t carry = carry_s;
     if (j < nblk) blocksum[j] = carry + ex;
     __syncthreads();
@@ -296,7 +277,7 @@ __global__ void k_scan_blocksum(const uint64_t* __restrict__ bits, int64_t nword
   for (int j = 0; j < kWordsPerThread; ++j)
     if (w0 + j < nwords) s += __popcll(bits[w0 + j]);
   uint32_t total;
-  block_exclusive_scan(s, &total);
+  spx_block_excl_scan(s, &total);
   if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
 }
 
@@ -318,7 +299,7 @@ __global__ void k_scan_expand(const uint64_t* __restrict__ bits, int64_t nwords,
     wv[j] = (w0 + j < nwords) ? bits[w0 + j] : 0ull;
     s += __popcll(wv[j]);
   }
-  uint32_t run = blocksum[blockIdx.x] + block_exclusive_scan(s, nullptr);
+  uint32_t run = blocksum[blockIdx.x] + spx_block_excl_scan(s, nullptr);
 #pragma unroll
   for (int j = 0; j < kWordsPerThread; ++j) {
     if (w0 + j >= nwords) break;
@@ -711,7 +692,7 @@ __global__ void k_dyn_offsets(const int32_t* __restrict__ count, const int64_t* 
     const int64_t j = base + threadIdx.x;
     const uint32_t v = j < nv ? (uint32_t)count[j] : 0u;
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan(v, &total);
+    const uint32_t ex = spx_block_excl_scan(v, &total);
     const uint32_t carry = carry_s;
     if (j < nv) offset[j] = (int32_t)(carry + ex);
     __syncthreads();

@@ -9,13 +9,12 @@
 // one gather of C-float rows and three multiply-adds per slot; only (M, C) outputs reach memory.  The statistics that
 // BatchNorm2d needs in training are the first and second moments of the offsets (nine numbers), summed here in double.
 // Backward, deterministic (no float atomics):
-//   df[r, c]  = sum of dout[m, c] over the (m, c) whose winning slot points at r: the (m, s) entries are stable-radix-
-//               sorted by r, then every (r, c) walks its run in ascending m (the scheme of spx_group_project_bwd);
+//   df[r, c]  = sum of dout[m, c] over the (m, c) whose winning slot points at r: sorted runs of the (m, s) entries by
+//               r (sorted_runs.h), then every (r, c) walks its run in ascending m;
 //   dA, db    = each block sums a fixed chunk of queries (one wave per query, strided, then the four waves in order),
 //               one block per output then adds the per-block partials in a fixed order.
-#include "spx_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "block_ops.h"
+#include "sorted_runs.h"
 
 namespace {
 
@@ -120,12 +119,6 @@ __global__ __launch_bounds__(kThreads) void k_vp_fwd(const float* __restrict__ f
 }
 
 // ---------------------------------------------------------------------------------------------- moments
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, SPX_WAVE);
-  return v;
-}
-
 // part[blk][9] = (sum d, upper triangle of sum d d^T) over the block's kMomCols columns
 __global__ __launch_bounds__(kThreads) void k_vp_mom_part(const float* __restrict__ xyz,
                                                           const float* __restrict__ new_xyz,
@@ -161,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void k_vp_mom_part(const float* __restric
   }
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
-    const double v = wave_sum(acc[q]);
+    const double v = spx_wave_sum(acc[q]);
     if (lane == 0) s_w[wave][q] = v;
   }
   __syncthreads();
@@ -171,23 +164,6 @@ __global__ __launch_bounds__(kThreads) void k_vp_mom_part(const float* __restric
     for (int w = 1; w < kWaves; ++w) v += s_w[w][tid];
     part[(size_t)blockIdx.x * 9 + tid] = v;
   }
-}
-
-// out[q] = sum over blocks of part[blk][q]: one block per q, thread t adds blocks t, t + 256, ... then a fixed tree
-template <typename T>
-__global__ __launch_bounds__(kThreads) void k_vp_final(const T* __restrict__ part, int64_t nblk, int nq,
-                                                       T* __restrict__ out) {
-  __shared__ T s_v[kThreads];
-  const int q = blockIdx.x, tid = threadIdx.x;
-  T v = 0;
-  for (int64_t k = tid; k < nblk; k += kThreads) v += part[(size_t)k * nq + q];
-  s_v[tid] = v;
-  __syncthreads();
-  for (int h = kThreads / 2; h > 0; h >>= 1) {
-    if (tid < h) s_v[tid] += s_v[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[q] = s_v[0];
 }
 
 // ---------------------------------------------------------------------------------------------- df
@@ -200,17 +176,6 @@ __global__ __launch_bounds__(kThreads) void k_vp_keys(const int32_t* __restrict_
   if (!(empty && empty[m])) r = slot_row(g, idx, m, (int)(col - m * g.nsample));
   keys[col] = r < 0 ? (uint32_t)g.n_src : (uint32_t)r;
   vals[col] = (uint32_t)col;
-}
-
-__global__ __launch_bounds__(kThreads) void k_vp_bounds(const uint32_t* __restrict__ keys, int64_t total,
-                                                        uint32_t sentinel, int32_t* __restrict__ start,
-                                                        int32_t* __restrict__ end) {
-  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (q >= total) return;
-  const uint32_t k = keys[q];
-  if (k == sentinel) return;
-  if (q == 0 || keys[q - 1] != k) start[k] = (int32_t)q;
-  if (q == total - 1 || keys[q + 1] != k) end[k] = (int32_t)(q + 1);
 }
 
 // df[r, c] = sum over r's sorted run of dout[m, c] where the winning slot of (m, c) is the entry's, in ascending m
@@ -292,12 +257,6 @@ __global__ __launch_bounds__(kThreads) void k_vp_dab_split(const float* __restri
   }
 }
 
-unsigned key_bits(uint64_t sentinel) {
-  unsigned bits = 1;
-  while (bits < 32 && (sentinel >> bits) != 0) ++bits;
-  return bits;
-}
-
 int check_geom(int32_t c, int64_t n_src, int64_t m, int32_t nsample, Geom* g) {
   if (c <= 0 || n_src < 0 || m < 0 || nsample <= 0) return SPX_ERR_INVALID_ARG;
   if (c > 65535 || n_src >= (int64_t)UINT32_MAX || m >= (int64_t)INT32_MAX) return SPX_ERR_TOO_LARGE;
@@ -314,34 +273,19 @@ int check_geom(int32_t c, int64_t n_src, int64_t m, int32_t nsample, Geom* g) {
 int64_t mom_blocks(int64_t total) { return (total + kMomCols - 1) / kMomCols; }
 int64_t dab_chunks(int64_t m) { return (m + kQChunk - 1) / kQChunk; }
 
-struct BwdWs {
-  uint32_t *keys_in, *vals_in, *keys_out, *vals_out;
-  int32_t *start, *end;
-  void* sort_tmp;
-  float *part, *dab4;
-  size_t sort_bytes;
+struct BwdWs : SortedRunsWs {
+  float *part, *dab4;   // dA / db: [dab_chunks][c][4] partials, [c][4] sums
 };
 
+// the sorted-runs block, then part | dab4
 size_t bwd_ws_layout(const Geom& g, char* base, BwdWs* ws) {
-  size_t sort_bytes = 0;
-  (void)rocprim::radix_sort_pairs((void*)nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)g.total, 0,
-                                  key_bits((uint64_t)g.n_src));
-  const size_t a = spx_align((size_t)g.total * 4), t = spx_align((size_t)g.n_src * 4), sb = spx_align(sort_bytes);
+  const size_t sr = spx_sorted_runs_layout(g.total, g.n_src, base, ws);
   const size_t pb = spx_align((size_t)dab_chunks(g.m) * g.c * 4 * 4), fb = spx_align((size_t)g.c * 4 * 4);
   if (ws) {
-    ws->keys_in = (uint32_t*)base;
-    ws->vals_in = (uint32_t*)(base + a);
-    ws->keys_out = (uint32_t*)(base + 2 * a);
-    ws->vals_out = (uint32_t*)(base + 3 * a);
-    ws->start = (int32_t*)(base + 4 * a);
-    ws->end = (int32_t*)(base + 4 * a + t);
-    ws->sort_tmp = base + 4 * a + 2 * t;
-    ws->part = (float*)(base + 4 * a + 2 * t + sb);
-    ws->dab4 = (float*)(base + 4 * a + 2 * t + sb + pb);
-    ws->sort_bytes = sb;
+    ws->part = (float*)(base + sr);
+    ws->dab4 = (float*)(base + sr + pb);
   }
-  return 4 * a + 2 * t + sb + pb + fb;
+  return sr + pb + fb;
 }
 
 }  // namespace
@@ -367,7 +311,7 @@ extern "C" int spx_voxel_pool_moments(const float* xyz, const float* new_xyz, co
   double* part = (double*)ws;
   if (nblk > 0)
     hipLaunchKernelGGL(k_vp_mom_part, dim3((unsigned)nblk), dim3(kThreads), 0, s, xyz, new_xyz, idx, empty, g, part);
-  hipLaunchKernelGGL((k_vp_final<double>), dim3(9), dim3(kThreads), 0, s, part, nblk, 9, moments);
+  hipLaunchKernelGGL(spx_k_column_sum<double>, dim3(9), dim3(256), 0, s, part, nblk, 9, moments);
   SPX_CHECK_LAUNCH();
   return SPX_OK;
 }
@@ -416,19 +360,10 @@ extern "C" int spx_voxel_pool_max_bwd(const float* dout, const int32_t* arg, con
   bwd_ws_layout(g, (char*)ws, &L);
   hipStream_t s = spx_s(stream);
   if (df && n_src > 0) {
-    const uint32_t sentinel = (uint32_t)n_src;
-    const dim3 cols((unsigned)((g.total + kThreads - 1) / kThreads));
-    if (g.total > 0) {
-      hipLaunchKernelGGL(k_vp_keys, cols, dim3(kThreads), 0, s, idx, empty, g, L.keys_in, L.vals_in);
-      size_t sb = L.sort_bytes;
-      if (rocprim::radix_sort_pairs(L.sort_tmp, sb, L.keys_in, L.keys_out, L.vals_in, L.vals_out, (size_t)g.total, 0,
-                                    key_bits(sentinel), s) != hipSuccess)
-        return SPX_ERR_LAUNCH;
-    }
-    // start and end are adjacent in ws (with the alignment gap): one fill zeroes both
-    spx_fill_async(L.start, 0, (size_t)((char*)(L.end + n_src) - (char*)L.start), s);
     if (g.total > 0)
-      hipLaunchKernelGGL(k_vp_bounds, cols, dim3(kThreads), 0, s, L.keys_out, g.total, sentinel, L.start, L.end);
+      hipLaunchKernelGGL(k_vp_keys, dim3((unsigned)((g.total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, idx,
+                         empty, g, L.keys_in, L.vals_in);
+    if (const int e = spx_sorted_runs(L, g.total, n_src, s); e != SPX_OK) return e;
     const int64_t nt = n_src * c;
     hipLaunchKernelGGL(k_vp_df, dim3((unsigned)((nt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, dout, arg,
                        L.vals_out, L.start, L.end, g, df);
@@ -438,7 +373,7 @@ extern "C" int spx_voxel_pool_max_bwd(const float* dout, const int32_t* arg, con
     if (nchunk > 0)
       hipLaunchKernelGGL(k_vp_dab_part, dim3((unsigned)nchunk, (unsigned)((c + SPX_WAVE - 1) / SPX_WAVE)), dim3(kThreads),
                          0, s, dout, arg, idx, empty, xyz, new_xyz, g, L.part);
-    hipLaunchKernelGGL((k_vp_final<float>), dim3((unsigned)(c * 4)), dim3(kThreads), 0, s, L.part, nchunk, c * 4, L.dab4);
+    hipLaunchKernelGGL(spx_k_column_sum<float>, dim3((unsigned)(c * 4)), dim3(256), 0, s, L.part, nchunk, c * 4, L.dab4);
     hipLaunchKernelGGL(k_vp_dab_split, dim3((unsigned)((c * 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, L.dab4,
                        c, da, db);
   }

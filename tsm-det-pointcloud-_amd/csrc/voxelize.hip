@@ -13,7 +13,7 @@
 // Replaces spconv.utils.Point2VoxelCPU3d.point_to_voxel — reference call sites
 // pcdet/datasets/processor/data_processor.py:37-43,55 — plus the concatenation of
 // pcdet/datasets/dataset.py:161-229 and MeanVFE (pcdet/models/backbones_3d/vfe/mean_vfe.py:26-29).
-#include "spx_common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -132,28 +132,10 @@ __device__ __forceinline__ uint32_t is_creator(const VoxWs& w, int64_t p, int64_
   return (s >= 0 && w.top[(int64_t)s * T] == (int32_t)p) ? 1u : 0u;
 }
 
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wsum[4];
-  int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0;
-  for (int x = 0; x < wave; ++x) base += wsum[x];
-  if (total) *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return base + inc - v;
-}
-
 __global__ void k_vox_blocksum(int64_t n, int T, VoxWs w) {
   int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   uint32_t total;
-  block_excl_scan(is_creator(w, p, n, T), &total);
+  spx_block_excl_scan(is_creator(w, p, n, T), &total);
   if (threadIdx.x == 0) w.blocksum[blockIdx.x] = total;
 }
 
@@ -165,7 +147,7 @@ __global__ void k_vox_scan_top(VoxWs w) {
     int64_t j = base + threadIdx.x;
     uint32_t v = j < w.nblk ? w.blocksum[j] : 0;
     uint32_t total;
-    uint32_t ex = block_excl_scan(v, &total);
+    uint32_t ex = spx_block_excl_scan(v, &total);
     uint32_t carry = carry_s;
     if (j < w.nblk) w.blocksum[j] = carry + ex;
     __syncthreads();
@@ -179,7 +161,7 @@ __global__ void k_vox_rank(const float* __restrict__ pts, int64_t n, int stride,
                            VoxWs w) {
   int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   uint32_t f = is_creator(w, p, n, T);
-  uint32_t ex = w.blocksum[blockIdx.x] + block_excl_scan(f, nullptr);
+  uint32_t ex = w.blocksum[blockIdx.x] + spx_block_excl_scan(f, nullptr);
   if (p >= n) return;
   w.crank[p] = ex;
   int b = point_frame(pts, p, stride, batch_col);
