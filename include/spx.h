@@ -1289,6 +1289,75 @@ int spx_dense_post_process(const float *scores, const int32_t *labels, const flo
                            float *out_boxes, float *out_scores, int64_t *out_labels, void *ws, size_t ws_bytes,
                            spx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 30. Batched RoI-aware pooling that writes only the live cells, and ragged points in boxes (csrc/roiaware_sparse.hip)
+ *    replaces: the per-frame loop of PartA2FCHead.roiaware_pool and the lines after it (reference
+ *      pcdet/models/roi_heads/partA2_head.py:104-204): per frame two RoIAwarePool3d calls (avg over the 4 part
+ *      channels, max over the backbone channels) into dense (N, o, o, o, C) grids, sum(-1).nonzero() (a host read), the
+ *      gather of the non-empty cells and the fake_sparse_idx branch; and points_in_boxes_gpu over frames of unequal
+ *      length.
+ *    Semantics: §12's, verbatim (inside test, cell index, the first max_pts - 1 points per cell in ascending point
+ *      index, max with strict > in list order and no winner -> 0 / arg -1, avg = list-order sum / count, the backward's
+ *      grad * (1 / fmaxf(count, 1)) and its ascending-RoI order from 0.0f), extended to a batch:
+ *      b frames, n_per RoIs each; RoI row r = f * n_per + i sees only the points of frame f, the rows
+ *      [start_f, start_f + frame_cnt[f]) of points, start_f = frame_cnt[0] + ... + frame_cnt[f - 1].
+ *      rois [b * n_per, 7]; points [np, 4] = (frame, x, y, z), rows grouped by ascending frame (the frame column is not
+ *      read: frame_cnt decides); frame_cnt DEVICE int32[b]; part [np, 4]; rpn [np, c]; all fp32 contiguous.
+ *      pf = the row stride of the per-RoI point records: a HOST bound on the longest frame (np always suffices).
+ *    Emitted cells: a cell that keeps at least one point AND whose four averaged part values have a non-zero fp32 sum
+ *      ((a0 + a1) + a2) + a3.  Defined for non-negative part values (sigmoid outputs): the order of the adds then cannot
+ *      change whether the sum is zero.  Row order: ascending (r, x, y, z), the row-major order of nonzero().
+ *    Fake branch: fewer than 3 emitted cells in the whole batch -> one row (r, 0, 0, 0) per RoI holding that cell's pooled
+ *      values (zeros, cnt 0, arg -1 when it is empty); n_rows = b * n_per, faked = 1.  Decided on the device.
+ *    Static capacity: rows at and past n_rows are dead: features 0, cnt 0, arg -1, coords -1; consumers take n_rows as
+ *      their live count (no kernel of the library reads a dead row).  n_rows > rows: SPX_ERR_CAPACITY in d_status (nullable,
+ *      see spx_read_status) and the rows past the capacity are dropped (row_of_cell -1: no gradient either).  Counts that
+ *      are negative, exceed np in sum, or a frame longer than pf: SPX_ERR_CAPACITY in d_status, the spans clamped to the
+ *      arrays (never an access outside them).
+ *    Limits, else SPX_ERR_TOO_LARGE: b <= 256 (every workgroup sums the earlier counts); b * n_per <= 2^20 RoI rows (the
+ *      scan is ONE workgroup walking them 1024 at a time); each out size < 256, b * n_per * ox * oy * oz < 2^31 (cell
+ *      counters in LDS up to 8192 cells per RoI, in the workspace beyond); np, pf < 2^29 - 1, b * n_per * pf < 2^31,
+ *      np * c < 2^31, rows < 2^29, rows * c < 2^31.
+ *    Integer atomics only (the per-cell counters), no float atomics, no host read, bitwise reproducible, capturable.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The state of one collect call (point records, cell counts, lists, ranks): kept by the caller until the last pool /
+ *   backward call that belongs to it.  0 for arguments the calls below refuse. */
+size_t spx_roiaware_sparse_ws_bytes(int32_t b, int64_t n_per, int64_t pf, int32_t ox, int32_t oy, int32_t oz);
+
+/* Two launches: collect (one workgroup per RoI: its frame's points, the lists, which cells are emitted) and the scan.
+ *   -> n_rows DEVICE int64[1], faked DEVICE int32[1], both written on every call; ws: the state.
+ *   b * n_per == 0: n_rows = 0, faked = 0. */
+int spx_roiaware_sparse_collect(const float *rois, const float *points, const int32_t *frame_cnt, const float *part,
+                                int32_t b, int64_t n_per, int64_t np, int64_t pf, int32_t ox, int32_t oy, int32_t oz,
+                                int32_t max_pts, int64_t *n_rows, int32_t *faked, int32_t *d_status, void *ws,
+                                size_t ws_bytes, spx_stream_t stream);
+
+/* One launch (a wave per emitted row, its lanes over the 4 + c channels).  ws, n_rows, faked: of the collect call.
+ *   -> coords [rows, 4] int32 (r, x, y, z); out_part [rows, 4]; out_rpn [rows, c]; arg [rows, c] int32 (GLOBAL point
+ *      rows, -1: no winner); cnt [rows] int32; row_of_cell [b * n_per * ox * oy * oz] int32 (-1: no row).  Every element
+ *      written on every call; may be called again with another capacity. */
+int spx_roiaware_sparse_pool(const float *part, const float *rpn, int32_t b, int64_t n_per, int64_t np, int64_t pf,
+                             int32_t c, int32_t ox, int32_t oy, int32_t oz, int64_t rows, const int64_t *n_rows,
+                             const int32_t *faked, int32_t *row_of_cell, int32_t *coords, float *out_part,
+                             float *out_rpn, int32_t *arg, int32_t *cnt, int32_t *d_status, const void *ws,
+                             size_t ws_bytes, spx_stream_t stream);
+
+/* grad [rows, c] -> grad_in [np, c], every element written.  mode 0 = max (arg [rows, c] of the pool call; cnt unused),
+ *   1 = avg (cnt [rows]; arg unused; c = 4 for the part tensor).  One launch: a thread per (point, channel) walks the RoI
+ *   rows of its own frame in ascending r from 0.0f and adds, through row_of_cell, grad[row] where arg == p (max) or
+ *   grad[row] * (1 / fmaxf(cnt[row], 1)) (avg).  No sort, no atomics. */
+int spx_roiaware_sparse_bwd(const float *grad, const int32_t *arg, const int32_t *cnt, const int32_t *row_of_cell,
+                            const int32_t *frame_cnt, int32_t b, int64_t n_per, int64_t np, int64_t pf, int32_t c,
+                            int32_t ox, int32_t oy, int32_t oz, int64_t rows, int32_t mode, float *grad_in,
+                            const void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* points [np, 4] = (frame, x, y, z) in any row order, boxes [b, t, 7] -> box_idx [np] int32: the first box of the
+ *   point's own frame that holds it (spx_points_in_boxes' test, ascending box index), -1 when none or when the frame
+ *   value is outside [0, b).  np < 2^29 - 1, t < 2^31 / 7, b <= 65535 else SPX_ERR_TOO_LARGE.  One launch. */
+int spx_points_in_boxes_stack(const float *points, const float *boxes, int32_t b, int64_t np, int64_t t,
+                              int32_t *box_idx, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

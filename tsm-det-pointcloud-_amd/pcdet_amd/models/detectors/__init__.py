@@ -1,5 +1,6 @@
 from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
+from .part_a2_net import PartA2Net
 from .point_3dssd import Point3DSSD
 from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
@@ -13,6 +14,7 @@ __all__ = {
     'SECONDNetIoU': SECONDNetIoU,
     'VoxelRCNN': VoxelRCNN,
     'PVRCNN': PVRCNN,
+    'PartA2Net': PartA2Net,
     '3DSSD': Point3DSSD,
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,

@@ -1,3 +1,4 @@
+from .partA2_head import PartA2FCHead
 from .pvrcnn_head import PVRCNNHead
 from .roi_head_template import RoIHeadTemplate
 from .second_head import SECONDHead
@@ -8,6 +9,7 @@ __all__ = {
     'SECONDHead': SECONDHead,
     'VoxelRCNNHead': VoxelRCNNHead,
     'PVRCNNHead': PVRCNNHead,
+    'PartA2FCHead': PartA2FCHead,
 }
 
 # heads that read the keypoint features a PFE module writes (point_features, point_coords, point_cls_scores)

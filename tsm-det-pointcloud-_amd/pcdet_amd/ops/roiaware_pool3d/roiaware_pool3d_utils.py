@@ -13,7 +13,8 @@ from spx import ops
 
 from ...utils import common_utils
 
-__all__ = ["points_in_boxes_cpu", "points_in_boxes_gpu", "RoIAwarePool3d", "RoIAwarePool3dFunction"]
+__all__ = ["points_in_boxes_cpu", "points_in_boxes_gpu", "points_in_boxes_stack", "RoIAwarePool3d",
+           "RoIAwarePool3dFunction"]
 
 _CPU_MARGIN = np.float64(np.float32(1e-2))   # the reference's `const float MARGIN = 1e-2` widened for the double compare
 _CPU_CHUNK = 1 << 22                          # (box, point) pairs evaluated at once
@@ -65,6 +66,16 @@ def points_in_boxes_gpu(points, boxes):
     assert boxes.shape[0] == points.shape[0]
     assert boxes.shape[2] == 7 and points.shape[2] == 3
     return ops.points_in_boxes(points, boxes)
+
+
+def points_in_boxes_stack(points_bxyz, boxes):
+    """
+    :param points_bxyz: (N1 + N2 + ..., 4) [bs_idx, x, y, z], frames of any length
+    :param boxes: (B, T, 7), num_valid_boxes <= T
+    :return box_idxs_of_pts: (N1 + N2 + ...), the first box of the point's own frame holding it, background = -1
+    """
+    assert boxes.shape[2] == 7 and points_bxyz.shape[1] == 4
+    return ops.points_in_boxes_stack(points_bxyz, boxes)
 
 
 class RoIAwarePool3d(nn.Module):

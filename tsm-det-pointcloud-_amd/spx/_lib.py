@@ -215,6 +215,14 @@ SIGNATURES = {
     "spx_dense_post_process_ws_bytes": (_sz, [ctypes.c_int32, _i64, ctypes.c_int32, _i64, _i64]),
     "spx_dense_post_process": (_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _f32p, ctypes.c_int32,
                                       ctypes.c_float, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_roiaware_sparse_ws_bytes": (_sz, [ctypes.c_int32, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "spx_roiaware_sparse_collect": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, _i64] + [ctypes.c_int32] * 4 +
+                                    [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "spx_roiaware_sparse_pool": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, _i64] + [ctypes.c_int32] * 4 + [_i64] +
+                                 [_vp] * 10 + [_sz, _vp]),
+    "spx_roiaware_sparse_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _i64, _i64] + [ctypes.c_int32] * 4 +
+                                [_i64, ctypes.c_int32, _vp, _vp, _sz, _vp]),
+    "spx_points_in_boxes_stack": (_int, [_vp, _vp, ctypes.c_int32, _i64, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -2541,3 +2541,141 @@ def dense_post_process(scores, labels, boxes, batch_size, thresholds, nms_thresh
                                      _ptr(out["sel"]), _ptr(out["count"]), _ptr(out["boxes"]), _ptr(out["scores"]),
                                      _ptr(out["labels"]), _ptr(ws), wsb, _stream(scores)), "spx_dense_post_process")
     return out
+
+
+# ------------------------------------------------- sparse batched RoI-aware pooling, ragged points in boxes (§30)
+
+def points_in_boxes_stack(points_bxyz, boxes):
+    """spx_points_in_boxes_stack: points (P, 4) [frame, x, y, z] (frames of any length, any row order), boxes (B, M, 7)
+    -> (P) int32: the first box of the point's own frame holding it, or -1 (also for a frame outside [0, B))."""
+    _need_gpu(points_bxyz, boxes)
+    lib = _lib.load()
+    if points_bxyz.dim() != 2 or points_bxyz.shape[1] != 4 or boxes.dim() != 3 or boxes.shape[2] != 7:
+        raise _lib.SpxError("points_in_boxes_stack: points %s, boxes %s do not match (P, 4), (B, M, 7)"
+                            % (tuple(points_bxyz.shape), tuple(boxes.shape)))
+    points_bxyz, boxes = _f32(points_bxyz), _f32(boxes)
+    p = points_bxyz.shape[0]
+    out = torch.empty((p,), dtype=torch.int32, device=points_bxyz.device)
+    check(lib.spx_points_in_boxes_stack(_ptr(points_bxyz), _ptr(boxes), boxes.shape[0], p, boxes.shape[1], _ptr(out),
+                                        _stream(points_bxyz)), "spx_points_in_boxes_stack")
+    return out
+
+
+def frame_layout(bs_idx, batch_size):
+    """Rows per frame as a device int32 (B) (counted by comparison, as VoxelSetAbstraction.frame_counts: no bincount, no
+    host read) and the 0-dim device bool `layout_ok`: the rows are grouped by ascending frame."""
+    frames = torch.arange(batch_size, device=bs_idx.device, dtype=bs_idx.dtype)
+    cnt = (bs_idx.reshape(-1, 1) == frames.view(1, -1)).sum(dim=0).int()
+    ok = (bs_idx[1:] >= bs_idx[:-1]).all() & (cnt.sum() == bs_idx.numel())
+    return cnt, ok
+
+
+class RoiawareSparseState(object):
+    """What roiaware_sparse_collect hands to roiaware_sparse_pool: the inputs, the device record of the collection
+    (`ws`), and the device scalars n_rows (int64[1]), faked (int32[1]) and layout_ok (0-dim bool)."""
+    __slots__ = ("rois", "points", "part", "rpn", "part_in", "rpn_in", "frame_cnt", "layout_ok", "b", "n_per", "np",
+                 "pf", "out_size", "max_pts", "ws", "n_rows", "faked")
+
+
+def roiaware_sparse_collect(rois, points, part, rpn, out_size, max_pts_each_voxel, frame_cnt=None,
+                            max_frame_points=None):
+    """spx_roiaware_sparse_collect: rois (B, N, 7), points (P, 4) [frame, x, y, z] grouped by ascending frame, part
+    (P, 4) non-negative, rpn (P, C); frame_cnt the device int32 (B) rows per frame (None: frame_layout of the frame
+    column); max_frame_points a host bound on the longest frame (None: P) -> RoiawareSparseState.  Per RoI the point
+    lists, the cell counts and which cells are emitted; the scan over the B * N RoIs; n_rows and faked on the device.
+    No host read: the caller decides who reads n_rows."""
+    _need_gpu(rois, points, part, rpn, frame_cnt)
+    lib = _lib.load()
+    if rois.dim() != 3 or rois.shape[2] != 7 or points.dim() != 2 or points.shape[1] != 4 or part.dim() != 2 \
+            or tuple(part.shape) != (points.shape[0], 4) or rpn.dim() != 2 or rpn.shape[0] != points.shape[0]:
+        raise _lib.SpxError("roiaware_sparse_collect: rois %s, points %s, part %s, rpn %s do not match (B, N, 7), (P, 4), "
+                            "(P, 4), (P, C)" % (tuple(rois.shape), tuple(points.shape), tuple(part.shape),
+                                                tuple(rpn.shape)))
+    st = RoiawareSparseState()
+    st.part_in, st.rpn_in = part, rpn
+    st.rois, st.points, st.part, st.rpn = _f32(rois), _f32(points), _f32(part), _f32(rpn)
+    dev = st.points.device
+    st.b, st.n_per, st.np = int(rois.shape[0]), int(rois.shape[1]), int(points.shape[0])
+    if frame_cnt is None:
+        st.frame_cnt, st.layout_ok = frame_layout(st.points[:, 0], st.b)
+    else:
+        if frame_cnt.dtype != torch.int32 or frame_cnt.numel() != st.b:
+            raise _lib.SpxError("roiaware_sparse_collect: frame_cnt must be int32 (%d)" % st.b)
+        st.frame_cnt, st.layout_ok = frame_cnt.contiguous(), torch.ones((), dtype=torch.bool, device=dev)
+    st.pf = st.np if max_frame_points is None else min(int(max_frame_points), st.np)
+    st.out_size = tuple(int(v) for v in out_size)
+    st.max_pts = int(max_pts_each_voxel)
+    ox, oy, oz = st.out_size
+    wsb = lib.spx_roiaware_sparse_ws_bytes(st.b, st.n_per, st.pf, ox, oy, oz)
+    st.ws = torch.empty((max(int(wsb), 4),), dtype=torch.uint8, device=dev)
+    st.n_rows = torch.empty((1,), dtype=torch.int64, device=dev)
+    st.faked = torch.empty((1,), dtype=torch.int32, device=dev)
+    check(lib.spx_roiaware_sparse_collect(_ptr(st.rois), _ptr(st.points), _ptr(st.frame_cnt), _ptr(st.part), st.b,
+                                          st.n_per, st.np, st.pf, ox, oy, oz, st.max_pts, _ptr(st.n_rows),
+                                          _ptr(st.faked), _ptr(status_word(dev)), _ptr(st.ws), wsb, _stream(st.points)),
+          "spx_roiaware_sparse_collect")
+    return st
+
+
+def roiaware_sparse_pool_fwd(st, rows):
+    """spx_roiaware_sparse_pool on the state of roiaware_sparse_collect -> coords (rows, 4) int32 [r, x, y, z], part
+    (rows, 4), rpn (rows, C), arg (rows, C) int32 (point rows), cnt (rows) int32, row_of_cell (B * N * V) int32.  Rows at
+    and past n_rows are dead (features 0, coords -1); n_rows > rows sets the status word (check_status)."""
+    lib = _lib.load()
+    rows = int(rows)
+    dev = st.points.device
+    c = st.rpn.shape[1]
+    ox, oy, oz = st.out_size
+    coords = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+    out_part = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+    out_rpn = torch.empty((rows, c), dtype=torch.float32, device=dev)
+    arg = torch.empty((rows, c), dtype=torch.int32, device=dev)
+    cnt = torch.empty((rows,), dtype=torch.int32, device=dev)
+    row_of_cell = torch.empty((st.b * st.n_per * ox * oy * oz,), dtype=torch.int32, device=dev)
+    check(lib.spx_roiaware_sparse_pool(_ptr(st.part), _ptr(st.rpn), st.b, st.n_per, st.np, st.pf, c, ox, oy, oz, rows,
+                                       _ptr(st.n_rows), _ptr(st.faked), _ptr(row_of_cell), _ptr(coords), _ptr(out_part),
+                                       _ptr(out_rpn), _ptr(arg), _ptr(cnt), _ptr(status_word(dev)), _ptr(st.ws),
+                                       st.ws.numel(), _stream(st.points)), "spx_roiaware_sparse_pool")
+    return coords, out_part, out_rpn, arg, cnt, row_of_cell
+
+
+def roiaware_sparse_pool_bwd(st, grad, arg, cnt, row_of_cell, pool_method):
+    """spx_roiaware_sparse_bwd: grad (rows, C) -> (P, C); pool_method 0 = max (arg), 1 = avg (cnt).  Fixed order."""
+    lib = _lib.load()
+    grad = _f32(grad)
+    rows, c = grad.shape
+    ox, oy, oz = st.out_size
+    grad_in = torch.empty((st.np, c), dtype=torch.float32, device=grad.device)
+    check(lib.spx_roiaware_sparse_bwd(_ptr(grad), _ptr(arg), _ptr(cnt), _ptr(row_of_cell), _ptr(st.frame_cnt), st.b,
+                                      st.n_per, st.np, st.pf, c, ox, oy, oz, rows, int(pool_method), _ptr(grad_in),
+                                      _ptr(st.ws), st.ws.numel(), _stream(grad)), "spx_roiaware_sparse_bwd")
+    return grad_in
+
+
+class _RoiawareSparsePool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, part, rpn, st, rows):
+        coords, out_part, out_rpn, arg, cnt, row_of_cell = roiaware_sparse_pool_fwd(st, rows)
+        # The state (frame counts, the collection record) rides on ctx, not in save_for_backward, so autograd does not
+        # notice an in-place change of part / rpn between forward and backward.  That is harmless: the backward reads
+        # neither input, only grad, arg, cnt, row_of_cell (saved below) and the record of which point lies in which cell.
+        ctx.st = st
+        ctx.save_for_backward(arg, cnt, row_of_cell)
+        ctx.mark_non_differentiable(coords, arg, cnt, row_of_cell)
+        return out_part, out_rpn, coords, arg, cnt, row_of_cell
+
+    @staticmethod
+    def backward(ctx, d_part, d_rpn, *_unused):
+        arg, cnt, row_of_cell = ctx.saved_tensors
+        g_part = roiaware_sparse_pool_bwd(ctx.st, d_part, None, cnt, row_of_cell, 1) if ctx.needs_input_grad[0] else None
+        g_rpn = roiaware_sparse_pool_bwd(ctx.st, d_rpn, arg, None, row_of_cell, 0) if ctx.needs_input_grad[1] else None
+        return g_part, g_rpn, None, None
+
+
+def roiaware_sparse_pool(st, rows):
+    """The second call of the fused RoI-aware pooling (include/spx.h §30): writes `rows` rows (a capacity: the caller's
+    host copy of st.n_rows, or a static cap) -> dict(coords, part, rpn, arg, cnt, row_of_cell, n_rows, faked, layout_ok).
+    Differentiable in the part and rpn tensors given to roiaware_sparse_collect."""
+    out_part, out_rpn, coords, arg, cnt, row_of_cell = _RoiawareSparsePool.apply(st.part_in, st.rpn_in, st, int(rows))
+    return {"coords": coords, "part": out_part, "rpn": out_rpn, "arg": arg, "cnt": cnt, "row_of_cell": row_of_cell,
+            "n_rows": st.n_rows, "faked": st.faked, "layout_ok": st.layout_ok}
