@@ -988,7 +988,7 @@ int spx_center_head_loss(const float *hm, const float *heatmap, const float *con
                          size_t ws_bytes, spx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * 23. PillarVFE with one last-layer PFNLayer, forward + parameter gradients (csrc/pillar_vfe.hip)
+ * 23. PillarVFE with one last-layer PFNLayer, forward + parameter gradients (csrc/pillar_vfe.hip, csrc/pfn_layer.h)
  *    replaces: PillarVFE.forward + PFNLayer.forward for NUM_FILTERS of length 1 with USE_NORM (reference
  *      pcdet/models/backbones_3d/vfe/pillar_vfe.py:29-123): the feature cat, the mask multiply, Linear(C_in, 64,
  *      bias=False), BatchNorm1d between two permutes, ReLU and the max over the T rows of a pillar, each a pass over
@@ -1041,7 +1041,8 @@ int spx_pillar_vfe_bwd(const float *voxels, const int32_t *num_points, const int
                        size_t ws_bytes, spx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * 24. DynamicPillarVFE: sync-free pillarisation and one fused last-layer PFNLayerV2 (csrc/dyn_pillar_vfe.hip)
+ * 24. DynamicPillarVFE: sync-free pillarisation and one fused last-layer PFNLayerV2 (csrc/dyn_pillar_vfe.hip,
+ *     csrc/pfn_layer.h)
  *    replaces: DynamicPillarVFE.forward + PFNLayerV2.forward for NUM_FILTERS of length 1 with USE_NORM (reference
  *      pcdet/models/backbones_3d/vfe/dynamic_pillar_vfe.py:88-146): torch.unique over the cell keys (a sort and a host
  *      read), scatter_mean / scatter_max through torch_scatter (float atomics), the gathers by unq_inv and an [N, 64]

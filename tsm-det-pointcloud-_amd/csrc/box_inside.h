@@ -1,4 +1,5 @@
-// box_inside.h — the point-in-rotated-box test shared by roiaware_pool3d.hip (§12) and point_targets.hip (§16).
+// box_inside.h — the point-in-rotated-box test shared by roiaware_pool3d.hip (§12), roiaware_sparse.hip and
+// point_targets.hip (§16), and the RoI-aware cell of a local coordinate that the first two share.
 // The semantics are pinned in the header comment of roiaware_pool3d.hip and restated in tests/roiaware_ref.py.  The local
 // coordinates must not be contracted into FMAs: every file that includes this header sets `#pragma clang fp contract(off)`
 // itself, before its first function (the pragma of an including file covers the inline functions below).
@@ -39,4 +40,19 @@ __device__ __forceinline__ bool in_box(const BoxC& b, float x, float y, float z,
   lx = sx * b.cosa + sy * (-b.sina);   // contraction is off in every including file
   ly = sx * b.sina + sy * b.cosa;
   return (double)fabsf(lx) < b.lx && (double)fabsf(ly) < b.ly;
+}
+
+// float -> int as the hardware convert does it: saturating, NaN -> 0
+__device__ __forceinline__ int f2i_sat(float f) {
+  if (f != f) return 0;
+  if (f >= 2147483648.f) return INT32_MAX;
+  if (f <= -2147483648.f) return INT32_MIN;
+  return (int)f;
+}
+
+// the cell of a local coordinate along one axis of a box of size d cut into o cells, clamped to o - 1
+__device__ __forceinline__ unsigned cell_axis(float local, float d, int o) {
+  const float res = d / (float)o;
+  const unsigned u = (unsigned)f2i_sat((local + d / 2.f) / res);
+  return u < (unsigned)(o - 1) ? u : (unsigned)(o - 1);
 }

@@ -23,6 +23,8 @@
 
 #pragma clang fp contract(off)
 
+#include "score_keys.h"   // make_key, row_of (here: the flat heatmap index), sort_desc
+
 namespace {
 
 constexpr int kThreads = 1024;
@@ -57,19 +59,6 @@ struct SelLds {
   int hist[kBins];
   int n_valid, cnt, sel_bin, sel_rem, sel_cnt, kept;
 };
-
-// float -> uint32 whose unsigned order is the float order (-0 counts as +0, as in a float comparison)
-__device__ __forceinline__ uint32_t ordered_bits(float s) {
-  uint32_t u = __float_as_uint(s + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// never 0 (the index is below 2^31), so 0 marks an empty place
-__device__ __forceinline__ unsigned long long make_key(float v, int idx) {
-  return ((unsigned long long)ordered_bits(v) << 32) | (unsigned long long)(~(uint32_t)idx);
-}
-
-__device__ __forceinline__ int idx_of(unsigned long long key) { return (int)(~(uint32_t)key); }
 
 // hist[bin] += 1 for every lane with `on`.  Heatmap values crowd into a few bins of the leading digits, where one
 // atomic per lane would serialise on one address: the bins of the first two leading lanes are added once per wave.
@@ -162,25 +151,6 @@ __device__ int select_top(const unsigned long long (&key)[kPer], int k_top, SelL
   return min(s.cnt, k_top);
 }
 
-// bitonic sort of keys[0, p), descending; p a power of two; called by the whole workgroup after a barrier
-__device__ void sort_desc(unsigned long long* keys, int p) {
-  for (int k = 2; k <= p; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < p; i += blockDim.x) {
-        const int x = i ^ j;
-        if (x > i) {
-          const unsigned long long a = keys[i], b = keys[x];
-          const bool desc = (i & k) == 0;
-          if (desc ? a < b : a > b) {
-            keys[i] = b;
-            keys[x] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 // One output row from one selected key (or, without one, a row of zeros that is not kept).
 __device__ __forceinline__ bool decode_row(const DecodeArgs& a, int f, int j, bool have, unsigned long long key) {
   const int64_t o = (int64_t)f * a.k + j;
@@ -195,7 +165,7 @@ __device__ __forceinline__ bool decode_row(const DecodeArgs& a, int f, int j, bo
     return false;
   }
   const int hw = a.h * a.w;
-  const int idx = idx_of(key);                  // < n by construction
+  const int idx = row_of(key);                  // < n by construction
   const int cls = idx / hw, cell = idx - cls * hw;
   const int y = cell / a.w, x = cell - y * a.w;
   const float v = a.hm[(int64_t)f * a.n + idx];

@@ -18,41 +18,36 @@
 //                  O(n / 256) per thread whatever m is, and there are at most n / 2 048 such pillars.
 //   Nothing is serial in the size of a pillar.
 //
-// PFN layer.  Features live in the 13 fixed slots of pillar_vfe.hip (0-2 xyz, 3-5 xyz - pillar mean, 6-8 xyz - pillar
-// centre, 9 norm, 10-12 the raw columns past xyz) with the same slot -> weight-column table.  Tiles are 256 consecutive
-// positions of `order`, so the points of a pillar are contiguous and a pillar may span any number of tiles.
+// PFN layer.  The core — the 13 fixed feature slots and their slot -> weight-column table, the S1 / G statistics, the
+// BatchNorm fold and the closed-form weight gradient — is pfn_layer.h, shared with pillar_vfe.hip; the derivations are
+// there.  Tiles are 256 consecutive positions of `order`, so the points of a pillar are contiguous and a pillar may span
+// any number of tiles.  There are no padding rows: N is the number of kept points.
 // Training forward, five launches:
 //   1. k_mean: per pillar the mean of xyz, a double sum in a fixed order over `order` (one wave per pillar);
 //   2. k_stats: S1 = sum f and G = sum f f^T over the kept points, tile i to block i mod 1 024, one partial per block;
-//   3. k_stats_final: fixed-order sum of the partials, N = *d_num_points; per channel mean = w.S1 / N, E[x^2] = w^T G w / N,
-//      biased variance, invstd, folded scale / shift, running statistics (unbiased variance), the counter;
+//   3. k_stats_final: fixed-order sum of the partials, N = *d_num_points, then pfn_layer.h's per-channel statistics;
+//      the running statistics and the counter move only when N >= 2 (torch raises below two samples; here the status
+//      word says so);
 //   4. k_fwd: a wave walks 64 consecutive positions, lane = channel: z = (w.f) * scale + shift in double, ReLU, running max
 //      and the winning point row per pillar segment.  A pillar wholly inside the 64 positions is written at once; a segment
 //      cut by the chunk's edge goes to one of the chunk's two partial slots (head / tail);
 //   5. k_fwd_combine: one thread per (pillar, channel) joins the partials of a pillar that spans chunks, in position order
 //      (strict >, so ties keep the lowest position), and writes exact zeros to dead rows.
 // Eval forward: launches 1, 4, 5 with scale / shift folded from the running statistics.  The [N, 64] activations are
-// never written.  Backward, two launches, by the identity in the header of pillar_vfe.hip without its padding-row term.
+// never written.  Backward, two launches: k_bwd_gather takes A, d_beta, d_gamma of pfn_layer.h's dW formula (every selected
+// row is a real point), pfn_k_bwd_final applies it.
 //
 // Integer atomics only (bitmap OR, count, the large-pillar list; nothing that is kept depends on their order), no float
 // atomics, no host read, every floating sum in double in a fixed order.  Rows at or beyond min(*d_num_pillars, cap) and
 // positions at or beyond *d_num_points are never dereferenced.
 #include "block_ops.h"
+#include "pfn_layer.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSlots = 13;
-constexpr int kCout = 64;
-constexpr int kG = kSlots * kSlots;           // 169
-constexpr int kStat = kG + kSlots;            // 182: G then S1
-constexpr int kOffMean = kStat;               // stats[]: G, S1, mean[64], invstd[64], N
-constexpr int kOffInv = kStat + kCout;
-constexpr int kOffN = kStat + 2 * kCout;
-constexpr int kStatsLen = kOffN + 2;          // 312 doubles
 constexpr int kStatPart = 1024;               // partial-writing blocks of k_stats
 constexpr int kMaxPart = 256;                 // partial-writing blocks of k_bwd_gather
-constexpr int kAcc = kSlots + 2;              // per (block, channel): d_beta, d_gamma, A[13]
 constexpr int kSmall = 64;                    // bucket sizes: one wave / one block in LDS / compacting scan
 constexpr int kMedium = 2048;
 constexpr int kScanRows = 4 * kBlock;         // rows of `count` per block of the offset scan
@@ -337,25 +332,10 @@ struct In {
   int64_t n, cap;
 };
 
-struct BN {
-  const float *weight, *gamma, *beta;
-  float *running_mean, *running_var;
-  int64_t* nbt;
-  float momentum, eps;
-};
-
 __device__ __forceinline__ int64_t kept_points(const In& in) {
   int64_t v = *in.d_npts;
   if (v < 0) v = 0;
   return v < in.n ? v : in.n;
-}
-
-// A pillar centre in float32 with the product and the sum rounded separately, as the reference's two tensor ops round
-// them (hipcc contracts a * b + c into one fma by default).
-__device__ __forceinline__ float centre32(int32_t cell, float voxel, float offset) {
-#pragma clang fp contract(off)
-  const float prod = (float)cell * voxel;
-  return prod + offset;
 }
 
 // the 13 feature slots of point row i in pillar p (both already checked)
@@ -378,18 +358,6 @@ __device__ __forceinline__ void features(const In& in, const Geo& g, const doubl
   f[9] = sqrt(dx * dx + dy * dy + dz * dz);
 #pragma unroll
   for (int j = 0; j < 3; ++j) f[10 + j] = 3 + j < g.c ? (double)pt[3 + j] : 0.0;
-}
-
-__device__ __forceinline__ void load_w(const float* __restrict__ weight, const Geo& g, int ch, double* w) {
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) w[k] = g.col[k] >= 0 ? (double)weight[ch * g.c_in + g.col[k]] : 0.0;
-}
-
-__device__ __forceinline__ double dot13(const double* w, const double* __restrict__ f) {
-  double x = 0.0;
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) x = fma(w[k], f[k], x);
-  return x;
 }
 
 // one wave per pillar: lane l adds positions l, l + 64, ... in that order, then an xor butterfly
@@ -510,37 +478,7 @@ __global__ __launch_bounds__(kBlock) void k_stats_final(In in, Geo g, BN bn, con
     }
   }
   if (e >= kCout) return;
-  double w[kSlots];
-  load_w(bn.weight, g, e, w);
-  double mean = 0.0, var = 0.0;
-  if (n > 0.0) {
-    double sx = 0.0, sxx = 0.0;
-#pragma unroll
-    for (int a = 0; a < kSlots; ++a) {
-      sx = fma(w[a], s[kG + a], sx);
-      double r = 0.0;
-#pragma unroll
-      for (int b = 0; b < kSlots; ++b) r = fma(s[a * kSlots + b], w[b], r);
-      sxx = fma(w[a], r, sxx);
-    }
-    mean = sx / n;
-    var = sxx / n - mean * mean;
-    if (!(var > 0.0)) var = 0.0;
-  }
-  const double invstd = 1.0 / sqrt(var + (double)bn.eps);
-  const double scale = (double)bn.gamma[e] * invstd;
-  stats[kOffMean + e] = mean;
-  stats[kOffInv + e] = invstd;
-  save_mean[e] = (float)mean;
-  save_invstd[e] = (float)invstd;
-  ss[e] = scale;
-  ss[kCout + e] = (double)bn.beta[e] - mean * scale;
-  if (enough && bn.running_mean && bn.running_var) {
-    const double mo = (double)bn.momentum;
-    const double unbiased = var * (n / (n - 1.0));
-    bn.running_mean[e] = (float)((1.0 - mo) * (double)bn.running_mean[e] + mo * mean);
-    bn.running_var[e] = (float)((1.0 - mo) * (double)bn.running_var[e] + mo * unbiased);
-  }
+  stats_channel(bn, g, s, n, enough, e, stats, ss, save_mean, save_invstd);
 }
 
 // ss: the folded scale / shift of k_stats_final, or nullptr: fold the running statistics here (eval)
@@ -557,14 +495,7 @@ __global__ __launch_bounds__(kBlock) void k_fwd(In in, Geo g, BN bn, const doubl
   double w[kSlots];
   load_w(bn.weight, g, ch, w);
   double scale, shift;
-  if (ss) {
-    scale = ss[ch];
-    shift = ss[kCout + ch];
-  } else {
-    const double invstd = 1.0 / sqrt((double)bn.running_var[ch] + (double)bn.eps);
-    scale = (double)bn.gamma[ch] * invstd;
-    shift = (double)bn.beta[ch] - (double)bn.running_mean[ch] * scale;
-  }
+  fold_scale_shift(bn, ss, ch, scale, shift);
   __syncthreads();
   const int tb = q * 64;
   const int64_t cstart = pos0 + tb;
@@ -643,14 +574,7 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine(In in, const double* __r
 }
 
 // ------------------------------------------------------------------------------------------------------ backward
-struct Bwd {
-  const float *out, *d_out;       // [cap, 64]
-  const int32_t* arg;             // [cap, 64] point rows
-  const double* stats;            // forward's, training only
-  int training;
-};
-
-__global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd b, const double* __restrict__ pmean,
+__global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd<int32_t> b, const double* __restrict__ pmean,
                                                        double* __restrict__ part) {
   __shared__ double red[3 * kAcc * kCout];
   const int64_t live = live_rows(in.d_np, in.cap);
@@ -658,13 +582,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd 
   double w[kSlots];
   load_w(bn.weight, g, ch, w);
   double mean, invstd;
-  if (b.training) {
-    mean = b.stats[kOffMean + ch];
-    invstd = b.stats[kOffInv + ch];
-  } else {
-    mean = (double)bn.running_mean[ch];
-    invstd = 1.0 / sqrt((double)bn.running_var[ch] + (double)bn.eps);
-  }
+  mean_invstd(bn, b, ch, mean, invstd);
   double acc[kAcc];
 #pragma unroll
   for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
@@ -702,64 +620,13 @@ __global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_bwd_final(Geo g, BN bn, Bwd b, const double* __restrict__ part, int n_part,
-                                                      float* __restrict__ d_weight, float* __restrict__ d_gamma,
-                                                      float* __restrict__ d_beta) {
-  __shared__ double red[3 * kAcc * kCout];
-  const int q = threadIdx.x >> 6, ch = threadIdx.x & 63;
-  double acc[kAcc];
-#pragma unroll
-  for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
-  for (int blk = q; blk < n_part; blk += 4) {
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) acc[k] += part[((int64_t)blk * kAcc + k) * kCout + ch];
-  }
-  if (q > 0) {
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) red[((q - 1) * kAcc + k) * kCout + ch] = acc[k];
-  }
-  __syncthreads();
-  if (q != 0) return;
-#pragma unroll
-  for (int k = 0; k < kAcc; ++k)
-    for (int r = 0; r < 3; ++r) acc[k] += red[(r * kAcc + k) * kCout + ch];
-  const double db = acc[0], dg = acc[1];
-  double w[kSlots];
-  load_w(bn.weight, g, ch, w);
-  const double gamma = (double)bn.gamma[ch];
-  double dw[kSlots];
-  if (b.training) {
-    const double* __restrict__ s = b.stats;
-    const double n = s[kOffN], mean = s[kOffMean + ch], invstd = s[kOffInv + ch];
-    const double rn = n > 0.0 ? 1.0 / n : 0.0;
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) {
-      double gw = 0.0;
-#pragma unroll
-      for (int j = 0; j < kSlots; ++j) gw = fma(s[k * kSlots + j], w[j], gw);
-      const double s1 = s[kG + k];
-      dw[k] = gamma * invstd * (acc[2 + k] - db * rn * s1 - dg * rn * invstd * (gw - mean * s1));
-    }
-  } else {
-    const double invstd = 1.0 / sqrt((double)bn.running_var[ch] + (double)bn.eps);
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) dw[k] = gamma * invstd * acc[2 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k)
-    if (g.col[k] >= 0) d_weight[ch * g.c_in + g.col[k]] = (float)dw[k];
-  d_gamma[ch] = (float)dg;
-  d_beta[ch] = (float)db;
-}
-
-// Shared argument checks; fills the geometry and the slot -> column table.
+// Shared argument checks; fills the geometry and (make_cols) the slot -> column table.
 inline int make_geo(int64_t n, int stride, int xyz_col, int32_t c, int64_t cap, int32_t c_in, int32_t c_out,
                     const float* geom5, int use_absolute_xyz, int with_distance, Geo* g) {
   if (n < 0 || cap <= 0 || !geom5 || c < 3 || c > 6 || stride <= 0 || xyz_col < 0 || xyz_col + c > stride)
     return SPX_ERR_INVALID_ARG;
-  const int base = use_absolute_xyz ? c : c - 3;
-  if (c_in != base + 6 + (with_distance ? 1 : 0) || c_in > 16) return SPX_ERR_INVALID_ARG;
-  if (c_out != kCout) return SPX_ERR_UNSUPPORTED;
+  const int rc = make_cols(c, c_in, c_out, use_absolute_xyz, with_distance, g->col);
+  if (rc != SPX_OK) return rc;
   if (n >= (1ll << 31) || cap >= (1ll << 31) / kCout) return SPX_ERR_TOO_LARGE;
   g->vx = geom5[0];
   g->vy = geom5[1];
@@ -768,14 +635,6 @@ inline int make_geo(int64_t n, int stride, int xyz_col, int32_t c, int64_t cap, 
   g->oz = geom5[4];
   g->c = c;
   g->c_in = c_in;
-  const int x0 = use_absolute_xyz ? 3 : 0;      // first column of the raw features past xyz
-  for (int k = 0; k < 3; ++k) {
-    g->col[k] = use_absolute_xyz ? k : -1;
-    g->col[3 + k] = base + k;
-    g->col[6 + k] = base + 3 + k;
-    g->col[10 + k] = 3 + k < c ? x0 + k : -1;
-  }
-  g->col[9] = with_distance ? base + 6 : -1;
   return SPX_OK;
 }
 
@@ -929,13 +788,14 @@ extern "C" int spx_dynamic_pillar_vfe_bwd(const float* points, int64_t n_points,
   VWs w = v_layout(ws, n_points);
   In in{points, stride, xyz_col, coords, nullptr, nullptr, nullptr, d_num_pillars, nullptr, n_points, cap};
   BN bn{weight, gamma, nullptr, const_cast<float*>(running_mean), const_cast<float*>(running_var), nullptr, 0.f, eps};
-  Bwd b{out, d_out, arg, stats, training};
-  int np = 0;                     // no points: the gradients are zeros, from k_bwd_final alone
+  Bwd<int32_t> b{out, d_out, arg, stats, training};
+  int np = 0;                     // no points: the gradients are zeros, from pfn_k_bwd_final alone
   if (n_points > 0) {
     np = kMaxPart;
     hipLaunchKernelGGL(k_bwd_gather, dim3((unsigned)np), dim3(kBlock), 0, s, in, g, bn, b, pillar_mean, w.part);
   }
-  hipLaunchKernelGGL(k_bwd_final, dim3(1), dim3(kBlock), 0, s, g, bn, b, w.part, np, d_weight, d_gamma, d_beta);
+  hipLaunchKernelGGL((pfn_k_bwd_final<Geo, int32_t>), dim3(1), dim3(kBlock), 0, s, g, bn, b, w.part, np, d_weight, d_gamma,
+                     d_beta);
   SPX_CHECK_LAUNCH();
   return SPX_OK;
 }

@@ -5,46 +5,32 @@
 // Linear(C_in, 64, bias=False), BatchNorm1d over all M * T rows (padding rows are all-zero feature rows and COUNT), ReLU
 // and the max over the T rows of a pillar.  The composition writes an [M, T, 64] tensor five times; here it never exists.
 //
-// Features live in 13 FIXED slots whatever the configuration (0-2 xyz, 3-5 xyz - mean, 6-8 xyz - centre, 9 norm, 10-12
-// the raw columns past xyz); a host table maps every slot to its weight column (-1: absent, its weight reads as 0).  One
-// builder (build_tile) puts the features of 8 pillars x 32 point slots into LDS as doubles; every kernel goes through it,
-// so the statistics, the forward and the backward see identical features.
+// The PFN core — the 13 fixed feature slots and their slot -> weight-column table, the S1 / G statistics, the BatchNorm
+// fold and the closed-form weight gradient — is pfn_layer.h, shared with dyn_pillar_vfe.hip; the derivations are there.
+// One builder (build_tile) puts the features of 8 pillars x 32 point slots into LDS as doubles; every kernel goes through
+// it, so the statistics, the forward and the backward see identical features.
 //
 // Training forward, three launches:
 //   1. k_stats: S1 = sum f and G = sum f f^T over the real points (13 + 169 doubles), one partial per block;
-//   2. k_stats_final: fixed-order sum of the partials; per channel mean = w.S1 / N, E[x^2] = w^T G w / N, N = live rows * T,
-//      biased variance, invstd, the folded scale / shift, the running statistics (unbiased variance) and the counter.
-//      The linear layer is not evaluated for the statistics at all;
+//   2. k_stats_final: fixed-order sum of the partials, N = live rows * T (padding rows are all-zero feature rows and
+//      count), then pfn_layer.h's per-channel statistics, running update (whenever N > 0) and counter;
 //   3. k_fwd: one thread per (pillar, channel): x = w.f in double over the real points, z = x * scale + shift, the ReLU,
 //      the max and its index; a pillar with fewer than T points also offers relu(shift), the value of its padding rows.
 // Eval forward: launch 3 alone, scale / shift folded from the running statistics.
 //
-// Backward, two launches.  With g the gradient at the selected row of each (pillar, channel) where the output is
-// positive, the train-mode BatchNorm gradient of the weight is, per channel,
-//   dW = gamma invstd [ A - (d_beta / N) S1 - (d_gamma / N) invstd (G w - mean S1) ],
-//   A = sum g f_sel,  d_beta = sum g,  d_gamma = sum g xhat_sel   (xhat of a padding row = -mean invstd, its f = 0),
-// so the dense term needs only S1 and G of the forward; k_bwd_gather takes A, d_beta, d_gamma (one partial per block),
-// k_bwd_final adds them in a fixed order and applies the formula.
+// Backward, two launches: k_bwd_gather takes A, d_beta, d_gamma of pfn_layer.h's dW formula (one partial per block; a
+// selected padding row has f = 0 and xhat = -mean invstd), pfn_k_bwd_final adds them in a fixed order and applies it.
 //
 // No float atomics, no host read, every sum in double in a fixed order: outputs and gradients are bitwise reproducible,
 // and every launch shape depends on host values only (the live row count d_n is read on the device).
-#include "spx_common.h"
+#include "pfn_layer.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSlots = 13;
 constexpr int kTileP = 8;         // pillars per tile
 constexpr int kMaxT = 32;         // point slots per pillar
-constexpr int kCout = 64;
-constexpr int kG = kSlots * kSlots;           // 169
-constexpr int kStat = kG + kSlots;            // 182: G then S1
-constexpr int kOffMean = kStat;               // stats[]: G, S1, mean[64], invstd[64], N
-constexpr int kOffInv = kStat + kCout;
-constexpr int kOffN = kStat + 2 * kCout;
-constexpr int kStatsLen = kOffN + 2;          // 312 doubles
-constexpr int kMaxPart = 256;                 // partial-writing blocks of k_stats and k_bwd_gather
-constexpr int kAcc = kSlots + 2;              // per (block, channel): d_beta, d_gamma, A[13]
+constexpr int kMaxPart = 256;     // partial-writing blocks of k_stats and k_bwd_gather
 
 struct Geo {
   float vx, vy, vz, ox, oy, oz;
@@ -60,14 +46,6 @@ struct In {
   const int64_t* d_n;
   int64_t m;
 };
-
-// A pillar centre in float32 with the product and the sum rounded separately, as the reference's two tensor ops round
-// them (hipcc contracts a * b + c into one fma by default, also through __fmul_rn / __fadd_rn).
-__device__ __forceinline__ float centre32(int32_t cell, float voxel, float offset) {
-#pragma clang fp contract(off)
-  const float prod = (float)cell * voxel;
-  return prod + offset;
-}
 
 // Features of pillars [p0, p0 + 8) into fs[(p * 32 + t) * 13 + slot] for t < s_num[p]; s_num[p] = the row's point
 // count clamped to [0, T], 0 for a row at or beyond n_live (never dereferenced).  Thread = (p = tid >> 5, t = tid & 31).
@@ -122,18 +100,6 @@ __device__ __forceinline__ void build_tile(const In& in, const Geo& g, int64_t p
   f[12] = e[2];
 }
 
-__device__ __forceinline__ void load_w(const float* __restrict__ weight, const Geo& g, int ch, double* w) {
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) w[k] = g.col[k] >= 0 ? (double)weight[ch * g.c_in + g.col[k]] : 0.0;
-}
-
-__device__ __forceinline__ double dot13(const double* w, const double* __restrict__ f) {
-  double x = 0.0;
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) x = fma(w[k], f[k], x);
-  return x;
-}
-
 // ---------------------------------------------------------------------------------------------------- statistics
 __global__ __launch_bounds__(kBlock) void k_stats(In in, Geo g, double* __restrict__ part) {
   __shared__ double fs[kTileP * kMaxT * kSlots];
@@ -158,13 +124,6 @@ __global__ __launch_bounds__(kBlock) void k_stats(In in, Geo g, double* __restri
   if (e < kStat) part[(int64_t)blockIdx.x * kStat + e] = acc;
 }
 
-struct BN {
-  const float *weight, *gamma, *beta;
-  float *running_mean, *running_var;
-  int64_t* nbt;
-  float momentum, eps;
-};
-
 __global__ __launch_bounds__(kBlock) void k_stats_final(In in, Geo g, BN bn, const double* __restrict__ part, int n_part,
                                                         double* __restrict__ stats, double* __restrict__ ss,
                                                         float* __restrict__ save_mean, float* __restrict__ save_invstd) {
@@ -185,37 +144,7 @@ __global__ __launch_bounds__(kBlock) void k_stats_final(In in, Geo g, BN bn, con
     if (n > 0.0 && bn.nbt) bn.nbt[0] += 1;
   }
   if (e >= kCout) return;
-  double w[kSlots];
-  load_w(bn.weight, g, e, w);
-  double mean = 0.0, var = 0.0;
-  if (n > 0.0) {
-    double sx = 0.0, sxx = 0.0;
-#pragma unroll
-    for (int a = 0; a < kSlots; ++a) {
-      sx = fma(w[a], s[kG + a], sx);
-      double r = 0.0;
-#pragma unroll
-      for (int b = 0; b < kSlots; ++b) r = fma(s[a * kSlots + b], w[b], r);
-      sxx = fma(w[a], r, sxx);
-    }
-    mean = sx / n;
-    var = sxx / n - mean * mean;
-    if (!(var > 0.0)) var = 0.0;
-  }
-  const double invstd = 1.0 / sqrt(var + (double)bn.eps);
-  const double scale = (double)bn.gamma[e] * invstd;
-  stats[kOffMean + e] = mean;
-  stats[kOffInv + e] = invstd;
-  save_mean[e] = (float)mean;
-  save_invstd[e] = (float)invstd;
-  ss[e] = scale;
-  ss[kCout + e] = (double)bn.beta[e] - mean * scale;
-  if (n > 0.0 && bn.running_mean && bn.running_var) {
-    const double mo = (double)bn.momentum;
-    const double unbiased = n > 1.0 ? var * (n / (n - 1.0)) : var;
-    bn.running_mean[e] = (float)((1.0 - mo) * (double)bn.running_mean[e] + mo * mean);
-    bn.running_var[e] = (float)((1.0 - mo) * (double)bn.running_var[e] + mo * unbiased);
-  }
+  stats_channel(bn, g, s, n, n > 0.0, e, stats, ss, save_mean, save_invstd);
 }
 
 // ------------------------------------------------------------------------------------------------------- forward
@@ -241,14 +170,7 @@ __global__ __launch_bounds__(kBlock) void k_fwd(In in, Geo g, BN bn, const doubl
   double w[kSlots];
   load_w(bn.weight, g, ch, w);
   double scale, shift;
-  if (ss) {
-    scale = ss[ch];
-    shift = ss[kCout + ch];
-  } else {
-    const double invstd = 1.0 / sqrt((double)bn.running_var[ch] + (double)bn.eps);
-    scale = (double)bn.gamma[ch] * invstd;
-    shift = (double)bn.beta[ch] - (double)bn.running_mean[ch] * scale;
-  }
+  fold_scale_shift(bn, ss, ch, scale, shift);
   const double pad = shift > 0.0 ? shift : 0.0;
   __syncthreads();
   for (int h = 0; h < 2; ++h) {
@@ -281,14 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_fwd(In in, Geo g, BN bn, const doubl
 }
 
 // ------------------------------------------------------------------------------------------------------ backward
-struct Bwd {
-  const float *out, *d_out;       // [m, 64]
-  const uint8_t* arg;             // [m, 64]
-  const double* stats;            // forward's, training only
-  int training;
-};
-
-__global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd b, double* __restrict__ part) {
+__global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd<uint8_t> b, double* __restrict__ part) {
   __shared__ double fs[kTileP * kMaxT * kSlots];
   __shared__ int s_num[kTileP];
   const int64_t n_live = spx_live_n(in.d_n, in.m);
@@ -296,13 +211,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd 
   double w[kSlots];
   load_w(bn.weight, g, ch, w);
   double mean, invstd;
-  if (b.training) {
-    mean = b.stats[kOffMean + ch];
-    invstd = b.stats[kOffInv + ch];
-  } else {
-    mean = (double)bn.running_mean[ch];
-    invstd = 1.0 / sqrt((double)bn.running_var[ch] + (double)bn.eps);
-  }
+  mean_invstd(bn, b, ch, mean, invstd);
   double acc[kAcc];
 #pragma unroll
   for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
@@ -345,67 +254,16 @@ __global__ __launch_bounds__(kBlock) void k_bwd_gather(In in, Geo g, BN bn, Bwd 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_bwd_final(Geo g, BN bn, Bwd b, const double* __restrict__ part, int n_part,
-                                                      float* __restrict__ d_weight, float* __restrict__ d_gamma,
-                                                      float* __restrict__ d_beta) {
-  __shared__ double red[3 * kAcc * kCout];
-  const int q = threadIdx.x >> 6, ch = threadIdx.x & 63;
-  double acc[kAcc];
-#pragma unroll
-  for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
-  for (int blk = q; blk < n_part; blk += 4) {
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) acc[k] += part[((int64_t)blk * kAcc + k) * kCout + ch];
-  }
-  if (q > 0) {
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) red[((q - 1) * kAcc + k) * kCout + ch] = acc[k];
-  }
-  __syncthreads();
-  if (q != 0) return;
-#pragma unroll
-  for (int k = 0; k < kAcc; ++k)
-    for (int r = 0; r < 3; ++r) acc[k] += red[(r * kAcc + k) * kCout + ch];
-  const double db = acc[0], dg = acc[1];
-  double w[kSlots];
-  load_w(bn.weight, g, ch, w);
-  const double gamma = (double)bn.gamma[ch];
-  double dw[kSlots];
-  if (b.training) {
-    const double* __restrict__ s = b.stats;
-    const double n = s[kOffN], mean = s[kOffMean + ch], invstd = s[kOffInv + ch];
-    const double rn = n > 0.0 ? 1.0 / n : 0.0;
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) {
-      double gw = 0.0;
-#pragma unroll
-      for (int j = 0; j < kSlots; ++j) gw = fma(s[k * kSlots + j], w[j], gw);
-      const double s1 = s[kG + k];
-      dw[k] = gamma * invstd * (acc[2 + k] - db * rn * s1 - dg * rn * invstd * (gw - mean * s1));
-    }
-  } else {
-    const double invstd = 1.0 / sqrt((double)bn.running_var[ch] + (double)bn.eps);
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) dw[k] = gamma * invstd * acc[2 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k)
-    if (g.col[k] >= 0) d_weight[ch * g.c_in + g.col[k]] = (float)dw[k];
-  d_gamma[ch] = (float)dg;
-  d_beta[ch] = (float)db;
-}
-
 // The partial-writing grids do not depend on m: tile i always goes to block i % kMaxPart, so a call at static capacity
 // with d_n live rows adds the same numbers in the same order as the exact-size call on those rows.
 inline int n_part_of(int64_t) { return kMaxPart; }
 
-// Shared argument checks; fills the geometry and the slot -> column table.
+// Shared argument checks; fills the geometry and (make_cols) the slot -> column table.
 inline int make_geo(int64_t m, int32_t t, int32_t c, int32_t c_in, int32_t c_out, const float* geom6, int use_absolute_xyz,
                     int with_distance, Geo* g) {
   if (m < 0 || !geom6 || t < 1 || t > kMaxT || c < 3 || c > 6) return SPX_ERR_INVALID_ARG;
-  const int base = use_absolute_xyz ? c : c - 3;
-  if (c_in != base + 6 + (with_distance ? 1 : 0) || c_in > 16) return SPX_ERR_INVALID_ARG;
-  if (c_out != kCout) return SPX_ERR_UNSUPPORTED;
+  const int rc = make_cols(c, c_in, c_out, use_absolute_xyz, with_distance, g->col);
+  if (rc != SPX_OK) return rc;
   if (m * (int64_t)t * c >= (1ll << 40)) return SPX_ERR_TOO_LARGE;
   g->vx = geom6[0];
   g->vy = geom6[1];
@@ -414,16 +272,8 @@ inline int make_geo(int64_t m, int32_t t, int32_t c, int32_t c_in, int32_t c_out
   g->oy = geom6[4];
   g->oz = geom6[5];
   g->c = c;
-  g->t = t;
   g->c_in = c_in;
-  const int x0 = use_absolute_xyz ? 3 : 0;      // first column of the raw features past xyz
-  for (int k = 0; k < 3; ++k) {
-    g->col[k] = use_absolute_xyz ? k : -1;
-    g->col[3 + k] = base + k;
-    g->col[6 + k] = base + 3 + k;
-    g->col[10 + k] = 3 + k < c ? x0 + k : -1;
-  }
-  g->col[9] = with_distance ? base + 6 : -1;
+  g->t = t;
   return SPX_OK;
 }
 
@@ -491,14 +341,15 @@ extern "C" int spx_pillar_vfe_bwd(const float* voxels, const int32_t* num_points
   hipStream_t s = spx_s(stream);
   In in{voxels, num_points, coords, d_n, m};
   BN bn{weight, gamma, nullptr, const_cast<float*>(running_mean), const_cast<float*>(running_var), nullptr, 0.f, eps};
-  Bwd b{out, d_out, arg, stats, training};
+  Bwd<uint8_t> b{out, d_out, arg, stats, training};
   double* part = reinterpret_cast<double*>(ws);
-  int np = 0;                     // m == 0: the gradients are zeros, from k_bwd_final alone
+  int np = 0;                     // m == 0: the gradients are zeros, from pfn_k_bwd_final alone
   if (m > 0) {
     np = n_part_of(m);
     hipLaunchKernelGGL(k_bwd_gather, dim3((unsigned)np), dim3(kBlock), 0, s, in, g, bn, b, part);
   }
-  hipLaunchKernelGGL(k_bwd_final, dim3(1), dim3(kBlock), 0, s, g, bn, b, part, np, d_weight, d_gamma, d_beta);
+  hipLaunchKernelGGL((pfn_k_bwd_final<Geo, uint8_t>), dim3(1), dim3(kBlock), 0, s, g, bn, b, part, np, d_weight, d_gamma,
+                     d_beta);
   SPX_CHECK_LAUNCH();
   return SPX_OK;
 }

@@ -19,20 +19,12 @@
 
 #pragma clang fp contract(off)
 
+#include "point_dist.h"   // sq_dist, ord_f32: after the pragma, which covers them
+
 namespace {
 
 constexpr int kFpsMaxThreads = 1024;
 constexpr int kFpsRegPoints = 16;   // register-resident FPS: up to 16 points per thread, N <= 16384
-
-__device__ __forceinline__ float sq_dist(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return (dx * dx + dy * dy) + dz * dz;   // contraction is off for this file
-}
-
-__device__ __forceinline__ uint32_t ord_f32(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 int fps_log2_bs(int64_t n) {   // the reference's opt_n_threads, as log2
   int l = 0;

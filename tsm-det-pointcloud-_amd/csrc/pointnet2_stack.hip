@@ -21,22 +21,14 @@
 
 #pragma clang fp contract(off)
 
+#include "point_dist.h"   // sq_dist, ord_f32: after the pragma, which covers them
+
 namespace {
 
 constexpr int kMaxFrames = 256;
 constexpr int kTile = 256;     // queries per workgroup
 constexpr int kChunk = 512;    // source points staged in LDS at a time
 constexpr int kRunChunk = 128; // sorted entries per partial sum of the backward
-
-__device__ __forceinline__ float sq_dist(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return (dx * dx + dy * dy) + dz * dz;   // contraction is off for this file
-}
-
-__device__ __forceinline__ uint32_t ord_f32(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // s[0 .. b] = exclusive prefix sums of max(cnt, 0), each clamped to `rows`: s[f] is the first row of frame f and s[b]
 // the number of live rows.  Called by every thread of the workgroup; ends with a barrier.

@@ -1,8 +1,9 @@
 // post_nms.h — what the two post-processing files share (post_process.hip §15, dense_post_process.hip §29): the 64-bit
-// candidate keys, the LDS bitonic sort, the single-workgroup greedy NMS over a sorted list and the per-frame output
-// kernel.  Boxes are read by a row stride `ld` (>= 7 floats).
+// candidate keys and the LDS bitonic sort (score_keys.h), the single-workgroup greedy NMS over a sorted list and the
+// per-frame output kernel.  Boxes are read by a row stride `ld` (>= 7 floats).
 #pragma once
 #include "box_iou.h"
+#include "score_keys.h"
 
 namespace {
 
@@ -23,42 +24,10 @@ struct NmsLds {
   int cnt;
 };
 
-// float -> uint32 whose unsigned order is the float order (-0 counts as +0, as in a float comparison)
-__device__ __forceinline__ uint32_t ordered_bits(float s) {
-  uint32_t u = __float_as_uint(s + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// key of a member row: never 0, so 0 pads the sort
-__device__ __forceinline__ unsigned long long make_key(float score, int row) {
-  return ((unsigned long long)ordered_bits(score) << 32) | (unsigned long long)(~(uint32_t)row);
-}
-
-__device__ __forceinline__ int row_of(unsigned long long key) { return (int)(~(uint32_t)key); }
-
 __device__ __forceinline__ int pow2_at_least(int v) {
   int p = 1;
   while (p < v) p <<= 1;
   return p;
-}
-
-// bitonic sort of keys[0, p), descending; p a power of two; called by the whole workgroup after a barrier
-__device__ void sort_desc(unsigned long long* keys, int p) {
-  for (int k = 2; k <= p; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < p; i += blockDim.x) {
-        const int x = i ^ j;
-        if (x > i) {
-          const unsigned long long a = keys[i], b = keys[x];
-          const bool desc = (i & k) == 0;
-          if (desc ? a < b : a > b) {
-            keys[i] = b;
-            keys[x] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
 }
 
 template <bool NORMAL>

@@ -24,7 +24,7 @@
 
 #pragma clang fp contract(off)
 
-#include "box_inside.h"   // BoxC, box_consts, in_box: after the pragma, which covers them
+#include "box_inside.h"   // BoxC, box_consts, in_box, cell_axis: after the pragma, which covers them
 
 namespace {
 
@@ -32,20 +32,6 @@ constexpr int kPibThreads = 256;     // points_in_boxes: points per workgroup = 
 constexpr int kColThreads = 1024;    // collection: one workgroup per RoI
 constexpr int kColWaves = kColThreads / SPX_WAVE;
 constexpr int kLdsCells = 8192;      // voxel counters live in LDS up to this many cells per RoI, else in vox_cnt
-
-// float -> int as the hardware convert does it: saturating, NaN -> 0
-__device__ __forceinline__ int f2i_sat(float f) {
-  if (f != f) return 0;
-  if (f >= 2147483648.f) return INT32_MAX;
-  if (f <= -2147483648.f) return INT32_MIN;
-  return (int)f;
-}
-
-__device__ __forceinline__ unsigned cell_axis(float local, float d, int o) {
-  const float res = d / (float)o;
-  const unsigned u = (unsigned)f2i_sat((local + d / 2.f) / res);
-  return u < (unsigned)(o - 1) ? u : (unsigned)(o - 1);
-}
 
 // ------------------------------------------------------------------------------------------- points in boxes
 // grid (ceil(m / 256), b); each workgroup stages the frame's boxes 256 at a time with their constants and every thread

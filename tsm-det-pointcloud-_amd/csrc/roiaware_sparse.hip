@@ -25,7 +25,7 @@
 
 #pragma clang fp contract(off)
 
-#include "box_inside.h"   // BoxC, box_consts, in_box: after the pragma, which covers them
+#include "box_inside.h"   // BoxC, box_consts, in_box, cell_axis: after the pragma, which covers them
 
 namespace {
 
@@ -37,20 +37,6 @@ constexpr int kEmitThreads = 256;
 constexpr int kEmitWaves = kEmitThreads / SPX_WAVE;
 constexpr int kMaxFrames = 256;      // every thread sums the earlier frames' counts
 constexpr int64_t kMaxRois = 1 << 20;   // the single-workgroup scan walks them 1024 at a time
-
-// float -> int as the hardware convert does it: saturating, NaN -> 0 (roiaware_pool3d.hip)
-__device__ __forceinline__ int f2i_sat(float f) {
-  if (f != f) return 0;
-  if (f >= 2147483648.f) return INT32_MAX;
-  if (f <= -2147483648.f) return INT32_MIN;
-  return (int)f;
-}
-
-__device__ __forceinline__ unsigned cell_axis(float local, float d, int o) {
-  const float res = d / (float)o;
-  const unsigned u = (unsigned)f2i_sat((local + d / 2.f) / res);
-  return u < (unsigned)(o - 1) ? u : (unsigned)(o - 1);
-}
 
 // The rows of frame b: [start, start + len), clamped into [0, np] and to pf rows whatever the counts hold.  ok = the
 // counts were non-negative, fit into np and the frame into pf.

@@ -1831,8 +1831,21 @@ def pillar_vfe_c_in(c, use_absolute_xyz, with_distance):
     return (c + 6 if use_absolute_xyz else c + 3) + (1 if with_distance else 0)
 
 
-def _pillar_geom(voxel_size, offsets):
+def _pfn_geom(voxel_size, offsets):
     return f_arr([float(v) for v in voxel_size] + [float(v) for v in offsets])
+
+
+def _pfn_weight(what, weight, c, use_absolute_xyz, with_distance, dev):
+    """The weight checks of both PFN ops (§23, §24) -> C_in."""
+    c_in = pillar_vfe_c_in(c, use_absolute_xyz, with_distance)
+    if weight.dim() != 2 or weight.shape[1] != c_in or weight.dtype != torch.float32 or weight.device != dev:
+        raise _lib.SpxError("%s: weight %s %s is not float32 (C_out, %d) on %s: C = %d, use_absolute_xyz = %s, "
+                            "with_distance = %s" % (what, tuple(weight.shape), weight.dtype, c_in, dev, c,
+                                                    bool(use_absolute_xyz), bool(with_distance)))
+    if weight.shape[0] != PILLAR_VFE_C_OUT:
+        raise _lib.SpxError("%s: C_out = %d is not supported, the kernels are built for C_out = %d"
+                            % (what, weight.shape[0], PILLAR_VFE_C_OUT))
+    return c_in
 
 
 def _pillar_inputs(what, voxels, num_points, coords, weight, use_absolute_xyz, with_distance, d_n):
@@ -1849,14 +1862,7 @@ def _pillar_inputs(what, voxels, num_points, coords, weight, use_absolute_xyz, w
     if tuple(coords.shape) != (m, 4) or coords.device != dev or coords.dtype not in (torch.int32, torch.int64):
         raise _lib.SpxError("%s: coords %s %s on %s is not an integer (%d, 4) on %s"
                             % (what, tuple(coords.shape), coords.dtype, coords.device, m, dev))
-    c_in = pillar_vfe_c_in(c, use_absolute_xyz, with_distance)
-    if weight.dim() != 2 or weight.shape[1] != c_in or weight.dtype != torch.float32 or weight.device != dev:
-        raise _lib.SpxError("%s: weight %s %s is not float32 (C_out, %d) on %s: C = %d, use_absolute_xyz = %s, "
-                            "with_distance = %s" % (what, tuple(weight.shape), weight.dtype, c_in, dev, c,
-                                                    bool(use_absolute_xyz), bool(with_distance)))
-    if weight.shape[0] != PILLAR_VFE_C_OUT:
-        raise _lib.SpxError("%s: C_out = %d is not supported, the kernels are built for C_out = %d"
-                            % (what, weight.shape[0], PILLAR_VFE_C_OUT))
+    c_in = _pfn_weight(what, weight, c, use_absolute_xyz, with_distance, dev)
     if d_n is not None and isinstance(d_n, torch.Tensor) and d_n.dtype == torch.int32 and d_n.numel() == 1:
         d_n = d_n.to(torch.int64).view(1)              # a device cast, no host read
     d_n = _d_n("%s: d_n" % what, d_n, dev)
@@ -1871,6 +1877,48 @@ def _vec64(what, name, v, dev, dtype=torch.float32, n=PILLAR_VFE_C_OUT):
         raise _lib.SpxError("%s: %s %s %s on %s is not a contiguous %s (%d,) on %s"
                             % (what, name, tuple(v.shape), v.dtype, v.device, dtype, n, dev))
     return v
+
+
+def _pfn_bn(what, gamma, beta, running_mean, running_var, num_batches_tracked, training, dev):
+    """The forward's BatchNorm tensors, checked -> (gamma, beta, running_mean, running_var, nbt)."""
+    gamma = _vec64(what, "gamma", gamma.detach(), dev)
+    beta = _vec64(what, "beta", beta.detach(), dev)
+    running_mean = _vec64(what, "running_mean", running_mean, dev)
+    running_var = _vec64(what, "running_var", running_var, dev)
+    nbt = None
+    if num_batches_tracked is not None:
+        nbt = _vec64(what, "num_batches_tracked", num_batches_tracked.view(-1), dev, torch.int64, 1)
+    if not training and (running_mean is None or running_var is None):
+        raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    return gamma, beta, running_mean, running_var, nbt
+
+
+def _pfn_train_buffers(training, stats_len, dev):
+    """(mean, invstd (64,) float32, stats float64[stats_len()]) in training, else three None."""
+    if not training:
+        return None, None, None
+    return (torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev),
+            torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev),
+            torch.empty((int(stats_len()),), dtype=torch.float64, device=dev))
+
+
+def _pfn_bwd_state(what, weight, gamma, stats, stats_len, running_mean, running_var, training, dev):
+    """The backward's gamma and stats (training) or running statistics (eval), checked, and the three gradients ->
+    (gamma, stats, running_mean, running_var, d_weight, d_gamma, d_beta)."""
+    gamma = _vec64(what, "gamma", gamma.detach(), dev)
+    if training:
+        stats = _vec64(what, "stats", stats, dev, torch.float64, int(stats_len()))
+        if stats is None:
+            raise _lib.SpxError("%s: training mode needs the forward's stats" % what)
+    else:
+        running_mean = _vec64(what, "running_mean", running_mean, dev)
+        running_var = _vec64(what, "running_var", running_var, dev)
+        if running_mean is None or running_var is None:
+            raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    d_weight = torch.empty_like(weight)
+    d_gamma = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    d_beta = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    return gamma, stats, running_mean, running_var, d_weight, d_gamma, d_beta
 
 
 def pillar_vfe_fwd(voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, num_batches_tracked,
@@ -1889,22 +1937,11 @@ def pillar_vfe_fwd(voxels, num_points, coords, weight, gamma, beta, running_mean
     voxels, num, coords, weight, d_n, m, t, c, c_in = _pillar_inputs(what, voxels, num_points, coords, weight,
                                                                       use_absolute_xyz, with_distance, d_n)
     dev = voxels.device
-    gamma = _vec64(what, "gamma", gamma.detach(), dev)
-    beta = _vec64(what, "beta", beta.detach(), dev)
-    running_mean = _vec64(what, "running_mean", running_mean, dev)
-    running_var = _vec64(what, "running_var", running_var, dev)
-    nbt = None
-    if num_batches_tracked is not None:
-        nbt = _vec64(what, "num_batches_tracked", num_batches_tracked.view(-1), dev, torch.int64, 1)
-    if not training and (running_mean is None or running_var is None):
-        raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    gamma, beta, running_mean, running_var, nbt = _pfn_bn(what, gamma, beta, running_mean, running_var,
+                                                          num_batches_tracked, training, dev)
     out = torch.empty((m, PILLAR_VFE_C_OUT), dtype=torch.float32, device=dev)
     arg = torch.empty((m, PILLAR_VFE_C_OUT), dtype=torch.uint8, device=dev)
-    mean = invstd = stats = None
-    if training:
-        mean = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
-        invstd = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
-        stats = torch.empty((int(lib.spx_pillar_vfe_stats_len()),), dtype=torch.float64, device=dev)
+    mean, invstd, stats = _pfn_train_buffers(training, lib.spx_pillar_vfe_stats_len, dev)
     res = dict(out=out, arg=arg, mean=mean, invstd=invstd, stats=stats)
     if m == 0:
         if training:
@@ -1914,7 +1951,7 @@ def pillar_vfe_fwd(voxels, num_points, coords, weight, gamma, beta, running_mean
     ws = workspace(dev, wsb)
     check(lib.spx_pillar_vfe_fwd(_ptr(voxels), _ptr(num), _ptr(coords), m, _ptr(d_n), t, c, _ptr(weight), c_in,
                                  weight.shape[0], _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(nbt),
-                                 float(momentum), float(eps), _pillar_geom(voxel_size, offsets),
+                                 float(momentum), float(eps), _pfn_geom(voxel_size, offsets),
                                  1 if use_absolute_xyz else 0, 1 if with_distance else 0, 1 if training else 0, _ptr(out),
                                  _ptr(arg), _ptr(mean), _ptr(invstd), _ptr(stats), _ptr(ws), wsb, _stream(voxels)),
           "spx_pillar_vfe_fwd")
@@ -1938,26 +1975,15 @@ def pillar_vfe_bwd(d_out, out, arg, stats, voxels, num_points, coords, weight, g
         raise _lib.SpxError("%s: d_out %s, out %s %s, arg %s %s do not match float32 / float32 / uint8 %s"
                             % (what, tuple(d_out.shape), tuple(out.shape), out.dtype, tuple(arg.shape), arg.dtype, shape))
     d_out, out, arg = _f32(d_out), out.contiguous(), arg.contiguous()
-    gamma = _vec64(what, "gamma", gamma.detach(), dev)
-    if training:
-        stats = _vec64(what, "stats", stats, dev, torch.float64, int(lib.spx_pillar_vfe_stats_len()))
-        if stats is None:
-            raise _lib.SpxError("%s: training mode needs the forward's stats" % what)
-    else:
-        running_mean = _vec64(what, "running_mean", running_mean, dev)
-        running_var = _vec64(what, "running_var", running_var, dev)
-        if running_mean is None or running_var is None:
-            raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
-    d_weight = torch.empty_like(weight)
-    d_gamma = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
-    d_beta = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    gamma, stats, running_mean, running_var, d_weight, d_gamma, d_beta = _pfn_bwd_state(
+        what, weight, gamma, stats, lib.spx_pillar_vfe_stats_len, running_mean, running_var, training, dev)
     if m == 0:
         return d_weight.zero_(), d_gamma.zero_(), d_beta.zero_()
     wsb = lib.spx_pillar_vfe_ws_bytes(m)
     ws = workspace(dev, wsb)
     check(lib.spx_pillar_vfe_bwd(_ptr(voxels), _ptr(num), _ptr(coords), m, _ptr(d_n), t, c, _ptr(weight), c_in,
                                  weight.shape[0], _ptr(gamma), _ptr(running_mean), _ptr(running_var), float(eps),
-                                 _pillar_geom(voxel_size, offsets), 1 if use_absolute_xyz else 0,
+                                 _pfn_geom(voxel_size, offsets), 1 if use_absolute_xyz else 0,
                                  1 if with_distance else 0, 1 if training else 0, _ptr(out), _ptr(arg), _ptr(d_out),
                                  _ptr(stats) if training else None, _ptr(d_weight), _ptr(d_gamma), _ptr(d_beta), _ptr(ws),
                                  wsb, _stream(voxels)), "spx_pillar_vfe_bwd")
@@ -2080,19 +2106,8 @@ def _dyn_pillar_inputs(what, points, pillars, weight, use_absolute_xyz, with_dis
         raise _lib.SpxError("%s: no pillar rows (a cloud with no kept point has no batch statistics and no output)" % what)
     d_np = _d_n("%s: d_num_pillars" % what, pillars["d_num_pillars"], dev)
     d_npts = _d_n("%s: d_num_points" % what, pillars["d_num_points"], dev)
-    c_in = pillar_vfe_c_in(c, use_absolute_xyz, with_distance)
-    if weight.dim() != 2 or weight.shape[1] != c_in or weight.dtype != torch.float32 or weight.device != dev:
-        raise _lib.SpxError("%s: weight %s %s is not float32 (C_out, %d) on %s: C = %d, use_absolute_xyz = %s, "
-                            "with_distance = %s" % (what, tuple(weight.shape), weight.dtype, c_in, dev, c,
-                                                    bool(use_absolute_xyz), bool(with_distance)))
-    if weight.shape[0] != PILLAR_VFE_C_OUT:
-        raise _lib.SpxError("%s: C_out = %d is not supported, the kernels are built for C_out = %d"
-                            % (what, weight.shape[0], PILLAR_VFE_C_OUT))
+    c_in = _pfn_weight(what, weight, c, use_absolute_xyz, with_distance, dev)
     return points.contiguous(), weight.detach().contiguous(), d_np, d_npts, n, stride, c, c_in, cap
-
-
-def _dyn_pillar_geom(voxel_size, offsets):
-    return f_arr([float(voxel_size[0]), float(voxel_size[1])] + [float(v) for v in offsets])
 
 
 def dynamic_pillar_vfe_fwd(points, pillars, weight, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
@@ -2111,29 +2126,18 @@ def dynamic_pillar_vfe_fwd(points, pillars, weight, gamma, beta, running_mean, r
     points, weight, d_np, d_npts, n, stride, c, c_in, cap = _dyn_pillar_inputs(
         what, points, pillars, weight, use_absolute_xyz, with_distance, xyz_col, num_features)
     dev = points.device
-    gamma = _vec64(what, "gamma", gamma.detach(), dev)
-    beta = _vec64(what, "beta", beta.detach(), dev)
-    running_mean = _vec64(what, "running_mean", running_mean, dev)
-    running_var = _vec64(what, "running_var", running_var, dev)
-    nbt = None
-    if num_batches_tracked is not None:
-        nbt = _vec64(what, "num_batches_tracked", num_batches_tracked.view(-1), dev, torch.int64, 1)
-    if not training and (running_mean is None or running_var is None):
-        raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
+    gamma, beta, running_mean, running_var, nbt = _pfn_bn(what, gamma, beta, running_mean, running_var,
+                                                          num_batches_tracked, training, dev)
     out = torch.empty((cap, PILLAR_VFE_C_OUT), dtype=torch.float32, device=dev)
     arg = torch.empty((cap, PILLAR_VFE_C_OUT), dtype=torch.int32, device=dev)
     pmean = torch.empty((cap, 3), dtype=torch.float64, device=dev)
-    mean = invstd = stats = None
-    if training:
-        mean = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
-        invstd = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
-        stats = torch.empty((int(lib.spx_dynamic_pillar_vfe_stats_len()),), dtype=torch.float64, device=dev)
+    mean, invstd, stats = _pfn_train_buffers(training, lib.spx_dynamic_pillar_vfe_stats_len, dev)
     wsb = lib.spx_dynamic_pillar_vfe_ws_bytes(n)
     ws = workspace(dev, wsb)
     check(lib.spx_dynamic_pillar_vfe_fwd(
         _ptr(points), n, stride, xyz_col, c, _ptr(pillars["coords"]), _ptr(pillars["inverse"]), _ptr(pillars["offset"]),
         _ptr(pillars["order"]), cap, _ptr(d_np), _ptr(d_npts), _ptr(weight), c_in, weight.shape[0], _ptr(gamma), _ptr(beta),
-        _ptr(running_mean), _ptr(running_var), _ptr(nbt), float(momentum), float(eps), _dyn_pillar_geom(voxel_size, offsets),
+        _ptr(running_mean), _ptr(running_var), _ptr(nbt), float(momentum), float(eps), _pfn_geom(voxel_size[:2], offsets),
         1 if use_absolute_xyz else 0, 1 if with_distance else 0, 1 if training else 0, _ptr(out), _ptr(arg), _ptr(pmean),
         _ptr(mean), _ptr(invstd), _ptr(stats), _ptr(status_word(dev)), _ptr(ws), wsb, _stream(points)),
         "spx_dynamic_pillar_vfe_fwd")
@@ -2160,24 +2164,13 @@ def dynamic_pillar_vfe_bwd(d_out, out, arg, pillar_mean, stats, points, pillars,
                             "and float64 (%d, 3)" % (what, tuple(d_out.shape), tuple(out.shape), out.dtype, tuple(arg.shape),
                                                      arg.dtype, tuple(pillar_mean.shape), pillar_mean.dtype, shape, cap))
     d_out, out, arg, pillar_mean = _f32(d_out), out.contiguous(), arg.contiguous(), pillar_mean.contiguous()
-    gamma = _vec64(what, "gamma", gamma.detach(), dev)
-    if training:
-        stats = _vec64(what, "stats", stats, dev, torch.float64, int(lib.spx_dynamic_pillar_vfe_stats_len()))
-        if stats is None:
-            raise _lib.SpxError("%s: training mode needs the forward's stats" % what)
-    else:
-        running_mean = _vec64(what, "running_mean", running_mean, dev)
-        running_var = _vec64(what, "running_var", running_var, dev)
-        if running_mean is None or running_var is None:
-            raise _lib.SpxError("%s: eval mode needs running_mean and running_var" % what)
-    d_weight = torch.empty_like(weight)
-    d_gamma = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
-    d_beta = torch.empty((PILLAR_VFE_C_OUT,), dtype=torch.float32, device=dev)
+    gamma, stats, running_mean, running_var, d_weight, d_gamma, d_beta = _pfn_bwd_state(
+        what, weight, gamma, stats, lib.spx_dynamic_pillar_vfe_stats_len, running_mean, running_var, training, dev)
     wsb = lib.spx_dynamic_pillar_vfe_ws_bytes(n)
     ws = workspace(dev, wsb)
     check(lib.spx_dynamic_pillar_vfe_bwd(
         _ptr(points), n, stride, xyz_col, c, _ptr(pillars["coords"]), cap, _ptr(d_np), _ptr(weight), c_in, weight.shape[0],
-        _ptr(gamma), _ptr(running_mean), _ptr(running_var), float(eps), _dyn_pillar_geom(voxel_size, offsets),
+        _ptr(gamma), _ptr(running_mean), _ptr(running_var), float(eps), _pfn_geom(voxel_size[:2], offsets),
         1 if use_absolute_xyz else 0, 1 if with_distance else 0, 1 if training else 0, _ptr(out), _ptr(arg), _ptr(d_out),
         _ptr(pillar_mean), _ptr(stats) if training else None, _ptr(d_weight), _ptr(d_gamma), _ptr(d_beta), _ptr(ws), wsb,
         _stream(points)), "spx_dynamic_pillar_vfe_bwd")
